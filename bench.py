@@ -23,6 +23,13 @@ step 3 + GPU tile2csr (SURVEY.md §8d t_e2e).  Inputs are resident in HBM
                                         # sequential tile-row blocks of <= 1.5e9 products
                                         # each; every block's C stays on its device
 Rank 0 prints ONE JSON line.
+
+A plain run (no --full) sets up, warms up, times the steps, writes the last
+timed step's C if --dump-outputs is given, and prints the line.  Everything
+else the line can carry takes runs of its own and is measured only with --full:
+the stage breakdown (untimed steps with the stage events on), the
+reference-layout tiled leg, the CPU baseline and, at N > 1, the single-GPU time
+of the same product (scale_model's t1_ms and the speedups read against it).
 """
 import argparse
 import json
@@ -49,6 +56,8 @@ METRIC = "SpGEMM GFLOPS (fp64, C=A^2) + achieved HBM GB/s fraction, 1/2/4/8 MI35
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 XGMI_LINK_GBS = 153.0  # one xGMI link, per direction (MI355X_MICROARCH.md)
 STAGE_STEPS = 3  # untimed steps with the stage events on (bench.py stage_ms)
+DUMP_CAP = 1 << 20  # --dump-outputs: elements per array (fp64: 8 MiB each; three arrays and their sample positions)
+DUMP_SEED = 20260116  # the sample of a longer array: fixed, a function of its length only
 
 
 def log(*a):
@@ -310,6 +319,26 @@ def pmc_traffic(kernels, path):
     return (int(tot) if found else None), allk
 
 
+def dump_outputs(outdir, m, n, rowptr, col, val):
+    """The C a caller of the timed path received (torch tensors, device or host),
+    as <outdir>/{shape,rowptr,col,val}.npy in fp64.  An array longer than
+    DUMP_CAP is sampled at sorted positions drawn with a fixed seed from its
+    length alone (saved beside it as <name>_index.npy), so two builds that agree
+    on nnz(C) write the same positions."""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "shape.npy"), np.array([m, n, col.numel()], dtype=np.float64))
+    for name, t in (("rowptr", rowptr), ("col", col), ("val", val)):
+        ipath = os.path.join(outdir, name + "_index.npy")
+        if t.numel() > DUMP_CAP:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), DUMP_CAP))
+            t = t[torch.from_numpy(idx).to(t.device)]
+            np.save(ipath, idx.astype(np.float64))
+        elif os.path.exists(ipath):  # (an earlier, longer dump's sample)
+            os.remove(ipath)
+        np.save(os.path.join(outdir, name + ".npy"), t.to(torch.float64).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -326,8 +355,18 @@ def main():
     ap.add_argument("--row-start", type=int, default=0,
                     help="with --rows R: A = rows [ROW_START, ROW_START + R) (e.g. the LiveJournal "
                          "stand-in's heaviest row block; B whole)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the stage breakdown (stage_ms, from untimed "
+                         "steps with the stage events on), the reference-layout tiled leg (tiled), the CPU "
+                         "baseline (cpu_baseline) and, at N>1, the single-GPU time of the same product "
+                         "(scale_model t1_ms); without it the line holds None (stage times: 0) there")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, save the C of the last timed step (the arrays its caller "
+                         "received: the last row block's when the product runs as sequential blocks, rank 0's "
+                         "gathered C at N>1) as DIR/{shape,rowptr,col,val}.npy in fp64; arrays longer than "
+                         f"{DUMP_CAP} elements as a fixed seeded sample with DIR/<name>_index.npy beside")
     ap.add_argument("--cpu-budget-s", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--check", action="store_true",
                     help="add a checksum of the (gathered) C of the last step to the JSON line")
     ap.add_argument("--dump", default=None,
@@ -359,8 +398,10 @@ def main():
     ap.add_argument("--tiled", type=int, default=None,
                     help="also time the reference-layout host path tsg_tilespgemm (csr2tile tiles "
                          "in, tiled C out; the reference's timed region) -> t_kern_tiled_ms; "
-                         "default on at N=1 for matrices with <= 4e8 intermediate products")
+                         "default: on with --full at N=1 for matrices with <= 4e8 intermediate products")
     args = ap.parse_args()
+    if args.dump_outputs and args.leg == "tiled":
+        ap.error("--dump-outputs saves the device leg's C; --leg tiled returns the reference's tiled layout")
 
     import torch
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -559,6 +600,16 @@ def main():
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and args.steps > 0:
+        # the last timed step's C, before any later call resets the context that owns it
+        if gather:
+            if rank == 0:
+                g_rp, g_ci, g_vv = gathered[0]
+                dump_outputs(args.dump_outputs, m, nb, g_rp, g_ci, g_vv)
+        elif rank == 0:
+            cv = ctx.view_torch(c)
+            dump_outputs(args.dump_outputs, cv.m, cv.n, cv.rowptr, cv.col, cv.val)
+        torch.cuda.synchronize()
     compute_timed = compute_ms[-args.steps:]  # (the timed steps' compute times)
     if dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
@@ -603,7 +654,7 @@ def main():
         nnz_r = [int(x[1].item()) for x in allm]
         comp_r = [round(float(x[2].item()), 4) for x in allm]
         t1_ms = None
-        if gather and rank == 0:
+        if gather and rank == 0 and args.full:
             dA_full = DeviceCSR.from_host(m, n, rp, ci, vv)
             ts = []
             for _ in range(3):
@@ -646,7 +697,11 @@ def main():
     # ~2-3 us of GPU time, which the timed steps do not pay.  The median over
     # STAGE_STEPS such steps (the first of them is not dropped: warm by then).
     stage_src = "timed steps (TSG_STAGE_EVENTS=1 set by the caller)"
-    if os.environ.get("TSG_STAGE_EVENTS") != "1":
+    if os.environ.get("TSG_STAGE_EVENTS") != "1" and not args.full:
+        stage_src = ("timed steps with the stage events off: the row-merge and band paths record only "
+                     "t_step3_kernel_ms and t_e2e_ms there, their other times read 0 and gflops_kern is None "
+                     "(--full measures them in steps of their own)")
+    elif os.environ.get("TSG_STAGE_EVENTS") != "1":
         n_gm = len(gather_ms)
         os.environ["TSG_STAGE_EVENTS"] = "1"
         st_stages = []
@@ -758,12 +813,12 @@ def main():
         g_rp, g_ci, g_vv = (x.cpu().numpy() for x in gathered[0])
         np.savez(args.dump, rowptr=g_rp, col=g_ci, val=g_vv)
     tiled = None
-    want_tiled = args.tiled if args.tiled is not None else (world == 1 and nnzcub_full <= 4e8)
+    want_tiled = args.tiled if args.tiled is not None else (args.full and world == 1 and nnzcub_full <= 4e8)
     if want_tiled and rank == 0 and world == 1:
         tiled = tiled_leg(m, n, rp, ci, vv, mb, nb, rpb, cib, vvb, aat, tm, nnzcub_full)
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 cpu = cpu_baseline(m, n, rp, ci, vv, mb, nb, rpb, cib, vvb, args.cpu_budget_s)
             except Exception as e:  # the baseline is reported, never required

@@ -20,9 +20,11 @@ def _port():
         return s.getsockname()[1]
 
 
-def _bench(nproc, mtx, aat, scaling=None, extra=()):
+def _bench(nproc, mtx, aat, scaling=None, extra=(), full=True):
+    # --full: the line's legs that take runs of their own (here the stage steps and
+    # scale_model's single-GPU time; the CPU baseline and the tiled leg switched off)
     args = ["bench.py", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--check", "--tiled", "0",
-            "--gpus", str(nproc)]
+            "--gpus", str(nproc)] + (["--full"] if full else [])
     if mtx:
         args += ["--mtx", mtx, "--aat", str(aat)]
     if scaling:  # default invocation (no flag) = strong: north_star's partition + gather of C
@@ -160,3 +162,23 @@ def test_two_ranks_streaming_gather_arrays(tmp_path, nsub):
     for k in ("rowptr", "col", "val"):
         np.testing.assert_array_equal(a[k], b[k])
     assert two["check"] == one["check"]
+
+
+def test_plain_run_dumps_last_timed_step(tmp_path):
+    """A plain run (no --full) measures only the timed steps -- no tiled leg, no
+    CPU baseline -- and --dump-outputs writes the C of the last timed step as
+    fp64 .npy files, equal to the C the same process recomputes for --dump."""
+    import numpy as np
+    mtx = os.path.join(REPO, "tests", "golden", "fixtures", "x_powerlaw_400.mtx")
+    out, npz = tmp_path / "out", str(tmp_path / "c.npz")
+    line = _bench(1, mtx, 0, extra=("--dump-outputs", str(out), "--dump", npz), full=False)
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert line["tiled"] is None and line["cpu_baseline"] is None
+    assert "stage events off" in line["stage_ms_source"]
+    ref = np.load(npz)
+    assert sorted(p.name for p in out.iterdir()) == ["col.npy", "rowptr.npy", "shape.npy", "val.npy"]
+    np.testing.assert_array_equal(np.load(out / "shape.npy"), [400, 400, len(ref["col"])])
+    for k in ("rowptr", "col", "val"):
+        got = np.load(out / (k + ".npy"))
+        assert got.dtype == np.float64
+        np.testing.assert_array_equal(got, ref[k])

@@ -14,8 +14,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 PS=${PSTEPS:-5}
-BENCH_PMC=(python3 "$ROOT/bench.py" --steps $PS --warmup 2 --no-cpu-baseline --tiled 0 "$@")
-BENCH_STATS=(python3 "$ROOT/bench.py" --steps $PS --warmup 2 --tiled 0 --pmc-from "$ROOT/profiles/${TAG}_pmc.json" "$@")
+BENCH_PMC=(python3 "$ROOT/bench.py" --full --steps $PS --warmup 2 --no-cpu-baseline --tiled 0 "$@")
+BENCH_STATS=(python3 "$ROOT/bench.py" --full --steps $PS --warmup 2 --tiled 0 --pmc-from "$ROOT/profiles/${TAG}_pmc.json" "$@")
 cd /tmp
 export TMPDIR=/tmp
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- "${BENCH_PMC[@]}" \

@@ -7,7 +7,7 @@ shift || true
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
-BENCH=(python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline "$@")
+BENCH=(python3 "$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline "$@")
 cd /tmp
 export TMPDIR=/tmp
 n=0

@@ -85,6 +85,7 @@ typedef struct tsg_stats {
 /* 1: retired (the fused element path of rounds 1-3; the row-merge path is faster on short rows too) */
 #define TSG_PATH_BAND 2   /* banded rows: dense LDS window per row */
 #define TSG_PATH_ROWS 3   /* row merge: rows binned by products, B runs merged in LDS */
+#define TSG_PATH_NUMERIC 4 /* numeric-only run on a known C pattern (tsg_dev_numeric_run) */
 
 /* ---------------- library / device ---------------- */
 const char *tsg_version(void);
@@ -148,6 +149,15 @@ int tsg_tile2csr(tsg_smatrix *C, int tile_size_m, int tile_size_n);
 int tsg_spgemm_csr(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C,
                    int tile_size_m, int tile_size_n, tsg_stats *stats);
 
+/* Numeric-only product on a known pattern: C->m, n, nnz, rowpointer and
+ * columnindex given (strictly ascending columns per row, containing A*B's
+ * structural pattern), C->value (malloc'd by the caller, nnz doubles)
+ * overwritten with the values of A*B.  Uploads the operands, creates a numeric
+ * plan (below), runs it once and destroys it.  TSG_ERR_INVALID for a malformed
+ * pattern or one that lacks a column of A*B (C->value is then unspecified).
+ * stats may be NULL. */
+int tsg_spgemm_csr_numeric(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, tsg_stats *stats);
+
 /* Frees every non-NULL pointer field and zeroes the struct (covers the
  * reference's matrix_destroy, src/csr2tile.h:509-518, and the CSR arrays). */
 void tsg_matrix_destroy(tsg_smatrix *M);
@@ -189,7 +199,8 @@ typedef struct tsg_dev_tiles {
  * tsg_dev_* calls made on it.  One stream per call; not thread-safe per context. */
 int tsg_context_create(int device, tsg_context **ctx);
 int tsg_context_destroy(tsg_context *ctx);
-/* Returns every context-owned output/temporary block to the cache. */
+/* Returns every context-owned output/temporary block to the cache (numeric
+ * plans keep their memory: it is not the cache's). */
 int tsg_context_reset(tsg_context *ctx);
 
 int tsg_dev_csr2tile_row_major(tsg_context *ctx, const tsg_dev_csr *A, int tile_size_m,
@@ -216,6 +227,54 @@ int tsg_dev_csr_rows_sorted(tsg_context *ctx, const tsg_dev_csr *M, void *stream
 int tsg_dev_spgemm_sorted_b(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B,
                             int b_checked_sorted, int tile_size_m, int tile_size_n, void *stream,
                             tsg_dev_csr *C, tsg_stats *stats);
+
+/* ---- numeric-only SpGEMM on a known C pattern ----
+ * For callers that multiply in a loop with fixed patterns and changing values
+ * (AMG setup, time stepping, Newton loops): the plan holds everything that
+ * depends on the patterns alone; a run computes c_val and nothing else -- no
+ * symbolic work, no allocation, no host read-back, C written once. */
+typedef struct tsg_numeric_plan tsg_numeric_plan;
+
+typedef struct tsg_numeric_info {
+    long long products;      /* sum over A entries of rowlen_B(col) */
+    long long nnzC;          /* pattern entries */
+    long long rows_class[4]; /* rows per class: packed / wave / workgroup / split */
+    long long split_units;   /* work units of the split class */
+    int b_rows_sorted;       /* what the plan found (1: every B row strictly column-sorted) */
+} tsg_numeric_info;
+
+/* Creates a plan for C = A*B on the three patterns.  The value fields of A, B
+ * and Cpattern are ignored.  The pattern arrays are device memory the caller
+ * keeps alive and unchanged for the plan's life.  C's pattern: strictly
+ * ascending columns per row, containing the structural pattern of A*B (a
+ * superset is allowed: entries no product reaches get 0.0).  B's rows need not
+ * be sorted and may repeat a column.
+ * All three patterns are validated on the device before anything indexes with
+ * them: rowpointer[0] == 0, non-decreasing, rowpointer[m] == nnz; A's and B's
+ * columns in [0, n); C's columns in [0, n) and strictly ascending per row;
+ * A->n == B->m, C->m == A->m, C->n == B->n.  Any violation returns
+ * TSG_ERR_INVALID and creates no plan (*plan = NULL).  Whether the pattern
+ * really contains A*B is not checked here; a run finds out (below).
+ * Synchronous; this is the one-off cost.
+ * Ownership: the plan's device memory is its own, outside the context's cache:
+ * it survives tsg_context_reset and every other tsg_dev_* call on the context.
+ * tsg_context_destroy destroys every plan still alive on the context; a plan
+ * must not be used or destroyed after its context. */
+int tsg_dev_numeric_plan_create(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B,
+                                const tsg_dev_csr *Cpattern, void *stream,
+                                tsg_numeric_plan **plan, tsg_numeric_info *info /*nullable*/);
+/* c_val[0..nnzC) := values of A*B for a_val / b_val laid on the plan's patterns
+ * (device pointers).  Synchronous on return, like tsg_dev_spgemm.  If a product's
+ * column is missing from its C row's pattern (the pattern is not a superset of
+ * A*B) nothing is written outside the row's own c_val range, the call returns
+ * TSG_ERR_INVALID and c_val's contents are unspecified; the plan stays usable.
+ * stats (nullable): t_e2e_ms, t_step3_kernel_ms (the numeric kernels), nnzCub
+ * (= products), nnzC, path = TSG_PATH_NUMERIC; the rest 0 or -1. */
+int tsg_dev_numeric_run(tsg_context *ctx, tsg_numeric_plan *plan, const double *a_val,
+                        const double *b_val, double *c_val, void *stream, tsg_stats *stats /*nullable*/);
+/* TSG_ERR_INVALID for a plan that is not alive on ctx (e.g. destroyed twice). */
+int tsg_dev_numeric_plan_destroy(tsg_context *ctx, tsg_numeric_plan *plan);
+
 /* Copies between host and device (stream-ordered, synchronous on return). */
 int tsg_memcpy_h2d(tsg_context *ctx, void *dst, const void *src, size_t bytes, void *stream);
 int tsg_memcpy_d2h(tsg_context *ctx, void *dst, const void *src, size_t bytes, void *stream);

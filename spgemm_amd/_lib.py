@@ -70,6 +70,16 @@ class DevTiles(C.Structure):
                                   "rm_mask", "rm_rowstart")]
 
 
+class NumericInfo(C.Structure):
+    """tsg_numeric_info, field for field."""
+    _fields_ = [("products", C.c_longlong), ("nnzC", C.c_longlong), ("rows_class", C.c_longlong * 4),
+                ("split_units", C.c_longlong), ("b_rows_sorted", C.c_int)]
+
+    def as_dict(self):
+        return dict(products=self.products, nnzC=self.nnzC, rows_class=list(self.rows_class),
+                    split_units=self.split_units, b_rows_sorted=self.b_rows_sorted)
+
+
 _lib = None
 
 _SIGS = {
@@ -89,6 +99,8 @@ _SIGS = {
     "tsg_tile2csr": ([C.POINTER(SMatrix), C.c_int, C.c_int], C.c_int),
     "tsg_spgemm_csr": ([C.POINTER(SMatrix), C.POINTER(SMatrix), C.POINTER(SMatrix), C.c_int, C.c_int,
                         C.POINTER(Stats)], C.c_int),
+    "tsg_spgemm_csr_numeric": ([C.POINTER(SMatrix), C.POINTER(SMatrix), C.POINTER(SMatrix), C.POINTER(Stats)],
+                               C.c_int),
     "tsg_matrix_destroy": ([C.POINTER(SMatrix)], None),
     "tsg_context_create": ([C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "tsg_context_destroy": ([C.c_void_p], C.c_int),
@@ -106,6 +118,11 @@ _SIGS = {
     "tsg_dev_spgemm_sorted_b": ([C.c_void_p, C.POINTER(DevCSR), C.POINTER(DevCSR), C.c_int, C.c_int, C.c_int,
                                  C.c_void_p, C.POINTER(DevCSR), C.POINTER(Stats)], C.c_int),
     "tsg_dev_csr_rows_sorted": ([C.c_void_p, C.POINTER(DevCSR), C.c_void_p, C.POINTER(C.c_int)], C.c_int),
+    "tsg_dev_numeric_plan_create": ([C.c_void_p, C.POINTER(DevCSR), C.POINTER(DevCSR), C.POINTER(DevCSR), C.c_void_p,
+                                     C.POINTER(C.c_void_p), C.POINTER(NumericInfo)], C.c_int),
+    "tsg_dev_numeric_run": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.POINTER(Stats)], C.c_int),
+    "tsg_dev_numeric_plan_destroy": ([C.c_void_p, C.c_void_p], C.c_int),
     "tsg_memcpy_h2d": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
     "tsg_memcpy_d2h": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
     "tsg_memcpy_d2d": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),

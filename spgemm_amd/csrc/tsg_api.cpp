@@ -140,9 +140,17 @@ static double ev_ms(hipEvent_t a, hipEvent_t b) {
 
 using namespace tsg;
 
+struct tsg_numeric_plan {
+    NumericPlan p;
+};
+
 struct tsg_context {
     Context cx;
     hipStream_t stream = nullptr;  // host-layer leases only (tsg_dev_* take the caller's stream)
+    // numeric plans alive on this context.  Their device memory is their own
+    // (not the pool's: a reset leaves it alone); tsg_context_destroy frees the
+    // ones still here, so a plan never outlives its context.
+    std::vector<tsg_numeric_plan *> plans;
 };
 
 // ------------------------------------------------------------------ helpers
@@ -879,6 +887,13 @@ int tsg_context_create(int device, tsg_context **ctx) {
 
 int tsg_context_destroy(tsg_context *ctx) {
     if (!ctx) return TSG_ERR_INVALID;
+    (void)hipSetDevice(ctx->cx.device);
+    (void)hipDeviceSynchronize();
+    for (tsg_numeric_plan *pl : ctx->plans) {  // (plans still alive go with their context)
+        dev_numeric_plan_free(pl->p);
+        delete pl;
+    }
+    ctx->plans.clear();
     ctx->cx.destroy();
     delete ctx;
     return TSG_OK;
@@ -1204,6 +1219,95 @@ int tsg_spgemm_csr(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, i
         if (rc == TSG_OK) rc = download(&C->columnindex, dC.columnindex, (size_t)dC.nnz, s);
         if (rc == TSG_OK) rc = download(&C->value, dC.value, (size_t)dC.nnz, s);
         if (rc == TSG_OK && hipStreamSynchronize(s) != hipSuccess) rc = TSG_ERR_HIP;
+    }
+    cx.pool.release_all_live();
+    return rc;
+}
+
+// ---- numeric-only product on a known C pattern (tsg_numeric.hip)
+int tsg_dev_numeric_plan_create(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B,
+                                const tsg_dev_csr *Cpattern, void *stream, tsg_numeric_plan **plan,
+                                tsg_numeric_info *info) {
+    if (plan) *plan = nullptr;
+    if (!ctx || !A || !B || !Cpattern || !plan) return TSG_ERR_INVALID;
+    tsg_numeric_plan *pl = new tsg_numeric_plan();
+    const int rc = dev_numeric_plan_create(ctx->cx, *A, *B, *Cpattern, pl->p, (hipStream_t)stream);
+    if (rc != TSG_OK) {
+        delete pl;
+        return rc;
+    }
+    ctx->plans.push_back(pl);
+    if (info) *info = pl->p.info;
+    *plan = pl;
+    return TSG_OK;
+}
+
+int tsg_dev_numeric_run(tsg_context *ctx, tsg_numeric_plan *plan, const double *a_val, const double *b_val,
+                        double *c_val, void *stream, tsg_stats *stats) {
+    if (!ctx || !plan || std::find(ctx->plans.begin(), ctx->plans.end(), plan) == ctx->plans.end())
+        return TSG_ERR_INVALID;
+    NumericPlan &p = plan->p;
+    if ((p.A.nnz && !a_val) || (p.B.nnz && !b_val) || (p.C.nnz && !c_val)) return TSG_ERR_INVALID;
+    Context &cx = ctx->cx;
+    auto h0 = std::chrono::steady_clock::now();
+    int missed = 0;
+    TSG_TRY(dev_numeric_run(cx, p, a_val, b_val, c_val, (hipStream_t)stream, stats ? cx.ev : nullptr, &missed));
+    if (stats) {
+        auto h1 = std::chrono::steady_clock::now();
+        tsg_stats st{};
+        st.numtileA = st.numtileB = st.numblkC = -1;
+        st.nnzCub = p.info.products;
+        st.nnzC = p.info.nnzC;
+        st.path = TSG_PATH_NUMERIC;
+        st.t_step3_kernel_ms = ev_ms(cx.ev[4], cx.ev[5]);
+        st.t_e2e_ms = std::chrono::duration<double, std::milli>(h1 - h0).count();
+        *stats = st;
+    }
+    return missed ? TSG_ERR_INVALID : TSG_OK;
+}
+
+int tsg_dev_numeric_plan_destroy(tsg_context *ctx, tsg_numeric_plan *plan) {
+    if (!ctx || !plan) return TSG_ERR_INVALID;
+    auto it = std::find(ctx->plans.begin(), ctx->plans.end(), plan);
+    if (it == ctx->plans.end()) return TSG_ERR_INVALID;
+    ctx->plans.erase(it);
+    dev_numeric_plan_free(plan->p);  // (runs are synchronous: nothing of the plan's is in flight)
+    delete plan;
+    return TSG_OK;
+}
+
+int tsg_spgemm_csr_numeric(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, tsg_stats *stats) {
+    if (!A || !B || !C || A->n != B->m || C->m != A->m || C->n != B->n) return TSG_ERR_INVALID;
+    if (A->nnz < 0 || B->nnz < 0 || C->nnz < 0 || A->m < 0 || B->m < 0) return TSG_ERR_INVALID;
+    if (!A->rowpointer || !B->rowpointer || !C->rowpointer) return TSG_ERR_INVALID;
+    if ((A->nnz && (!A->columnindex || !A->value)) || (B->nnz && (!B->columnindex || !B->value)) ||
+        (C->nnz && (!C->columnindex || !C->value)))
+        return TSG_ERR_INVALID;
+    HostLease lease;
+    TSG_TRY(lease.acquire());
+    Context &cx = lease.cx();
+    hipStream_t s = lease.stream();
+    tsg_dev_csr dA, dB, dC;
+    int rc = upload_csr(cx, A, dA, s);
+    if (rc == TSG_OK) rc = upload_csr(cx, B, dB, s);
+    if (rc == TSG_OK) {
+        dC.m = C->m; dC.n = C->n; dC.nnz = C->nnz;
+        rc = upload(cx, &dC.rowpointer, C->rowpointer, (size_t)C->m + 1, s);
+    }
+    if (rc == TSG_OK) rc = upload(cx, &dC.columnindex, C->columnindex, (size_t)C->nnz, s);
+    if (rc == TSG_OK) rc = cx.get(&dC.value, (size_t)C->nnz + 1);
+    if (rc == TSG_OK && hipStreamSynchronize(s) != hipSuccess) rc = TSG_ERR_HIP;
+    tsg_numeric_plan *plan = nullptr;
+    if (rc == TSG_OK) rc = tsg_dev_numeric_plan_create(lease.ctx(), &dA, &dB, &dC, s, &plan, nullptr);
+    if (rc == TSG_OK) {
+        rc = tsg_dev_numeric_run(lease.ctx(), plan, dA.value, dB.value, dC.value, s, stats);
+        if (rc == TSG_OK && C->nnz) {
+            if (hipMemcpyAsync(C->value, dC.value, (size_t)C->nnz * sizeof(double), hipMemcpyDeviceToHost, s) !=
+                    hipSuccess ||
+                hipStreamSynchronize(s) != hipSuccess)
+                rc = TSG_ERR_HIP;
+        }
+        (void)tsg_dev_numeric_plan_destroy(lease.ctx(), plan);
     }
     cx.pool.release_all_live();
     return rc;

@@ -197,6 +197,59 @@ int dev_scan_rows_fused(Context &cx, int *rp, int m, int *hnnz_dev, hipStream_t 
 // exclusive scan (n+1 idiom) whose total is read back
 int scan_exclusive_i32_total(Context &cx, int *a, long n, hipStream_t s, long long *total);
 
+// numeric-only product on a known C pattern (tsg_numeric.hip, DESIGN.md section
+// 3.7).  Rows are classed at plan time by len_C (the row's pattern entries) and
+// P (its element products); a row takes the first class both of whose caps it
+// fits, else it is split:
+//   0 packed     len_C <= 32    and P <= 512    16 lanes per row
+//   1 wave       len_C <= 512   and P <= 8,192  one wave per row (6 KiB of LDS), or a
+//                workgroup on a dense LDS window of the row's column span
+//   2 workgroup  len_C <= 4,096 and P <= 65,536 one workgroup per row (48 KiB of
+//                LDS: columns + fp64 sums at 12 B per entry, 3 workgroups per CU)
+//   3 split      the rest, in units of at most kNumUnitProducts products
+constexpr int kNumPackedLen = 32, kNumWaveLen = 512, kNumWgLen = 4096;
+constexpr long long kNumPackedProducts = 512, kNumWaveProducts = 8192, kNumWgProducts = 65536;
+constexpr int kNumUnitProducts = 4096;   // a split unit's products at most (16 per thread: the unit is one
+                                         //   chain of searches in global memory, its length is the run's tail)
+constexpr int kNumUnitEntries = 4096;    // and its A entries
+// the launch lists: a class's rows.  The wave class's rows of at least
+// kNumWindowProducts products whose columns span at most kNumWindow take the
+// dense-window kernel, the others the search; the searched wave and workgroup
+// rows of few pattern entries (most of them: the classes' lengths follow the
+// operands' power law) take an instantiation with a quarter of the LDS, so
+// that every wave slot of a CU is filled -- a row is a chain of dependent
+// loads, and the rows in flight are what hides it
+constexpr int kNumWindow = 2048;
+constexpr long long kNumWindowProducts = 1024;
+constexpr int kNumWaveSmallLen = 128, kNumWgSmallLen = 1024;
+enum { kNumListPacked = 0, kNumListWaveSmall, kNumListWave, kNumListWaveWin, kNumListWgSmall, kNumListWg,
+       kNumListSplit, kNumLists };
+inline int numeric_row_class(long long len_c, long long products) {
+    if (len_c <= kNumPackedLen && products <= kNumPackedProducts) return 0;
+    if (len_c <= kNumWaveLen && products <= kNumWaveProducts) return 1;
+    if (len_c <= kNumWgLen && products <= kNumWgProducts) return 2;
+    return 3;
+}
+struct NumericPlan {
+    tsg_dev_csr A{}, B{}, C{};  // the caller's pattern arrays (values unused)
+    void *block = nullptr;      // the plan's own hipMalloc block (not the pool's: survives a reset)
+    size_t bytes = 0;
+    int cnt[4] = {};            // rows per class (the info's counts)
+    int *rows = nullptr;        // the launch lists, list l at loff[l], lcnt[l] rows, ascending; the last
+                                //   (kNumLists) holds the rows with nothing to do
+    int lcnt[kNumLists + 1] = {}, loff[kNumLists + 1] = {};
+    int4 *units = nullptr;      // split units: (row, first A entry, A entries, B row offset or -1)
+    int nunits = 0;
+    int *miss = nullptr;        // device counter of products outside the pattern
+    int *hmiss = nullptr;       // its pinned host copy (the run's one D2H copy)
+    tsg_numeric_info info{};
+};
+int dev_numeric_plan_create(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &Cp,
+                            NumericPlan &p, hipStream_t s);
+int dev_numeric_run(Context &cx, NumericPlan &p, const double *a_val, const double *b_val, double *c_val,
+                    hipStream_t s, hipEvent_t *ev, int *missed);
+void dev_numeric_plan_free(NumericPlan &p);
+
 // read a device int / long long synchronously through pinned memory
 int read_i32(Context &cx, const int *d, int *h, hipStream_t s);
 int read_i64(Context &cx, const long long *d, long long *h, hipStream_t s);

@@ -7,7 +7,9 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import DevCSR, Stats, check, lib
+import weakref
+
+from ._lib import DevCSR, NumericInfo, Stats, check, lib
 
 
 class DeviceCSR:
@@ -31,8 +33,9 @@ class DeviceCSR:
         # loop should not pay for three data_ptr() calls and a ctypes struct per call)
         s = getattr(self, "_struct", None)
         if s is None:
+            # (val=None: a pattern only, for Context.numeric_plan)
             s = self._struct = DevCSR(self.m, self.n, self.nnz, self.rowpointer_ptr(), self.col.data_ptr(),
-                                      self.val.data_ptr())
+                                      self.val.data_ptr() if self.val is not None else None)
         return s
 
     def rowpointer_ptr(self):
@@ -42,18 +45,80 @@ class DeviceCSR:
         return (self.m, self.n, self.rowptr.cpu().numpy(), self.col.cpu().numpy(), self.val.cpu().numpy())
 
 
+class NumericPlan:
+    """A tsg_numeric_plan: C = A*B's values on a known C pattern, for products
+    repeated with fixed patterns and changing values.  Holds the three pattern
+    matrices (their tensors must stay alive and unchanged while the plan lives).
+    The plan's device memory survives Context.reset(); closing the context
+    closes its plans."""
+
+    def __init__(self, ctx, A, B, Cpattern, stream=None):
+        self.ctx, self.A, self.B, self.Cpattern = ctx, A, B, Cpattern
+        self.ptr = C.c_void_p()
+        info = NumericInfo()
+        a, b, c = A.struct(), B.struct(), Cpattern.struct()
+        s = C.c_void_p(stream) if stream else None
+        check("tsg_dev_numeric_plan_create", lib().tsg_dev_numeric_plan_create(
+            ctx.ptr, C.byref(a), C.byref(b), C.byref(c), s, C.byref(self.ptr), C.byref(info)))
+        self.info = info.as_dict()
+        self.nnzC = Cpattern.nnz
+
+    def run(self, a_val, b_val, out=None, stream=None, raw=False):
+        """out[0:nnzC] := values of A*B for the f64 device tensors a_val / b_val
+        laid on the plan's patterns.  Returns (out, stats).  Raises TsgError
+        (TSG_ERR_INVALID) when the pattern lacks a column of A*B."""
+        import torch
+        if not self.ptr:
+            raise RuntimeError("numeric plan is closed")
+        for t, n in ((a_val, self.A.nnz), (b_val, self.B.nnz)):
+            if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != n or not t.is_cuda:
+                raise ValueError("values: contiguous float64 device tensors of the patterns' nnz")
+        if out is None:
+            out = torch.empty(self.nnzC, dtype=torch.float64, device=a_val.device)
+        elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != self.nnzC or not out.is_cuda:
+            raise ValueError("out: a contiguous float64 device tensor of nnzC entries")
+        st = Stats()
+        s = C.c_void_p(stream) if stream else None
+        check("tsg_dev_numeric_run", lib().tsg_dev_numeric_run(
+            self.ctx.ptr, self.ptr, a_val.data_ptr(), b_val.data_ptr(), out.data_ptr(), s, C.byref(st)))
+        return out, (st if raw else st.as_dict())
+
+    def close(self):
+        if self.ptr and self.ctx.ptr:
+            lib().tsg_dev_numeric_plan_destroy(self.ctx.ptr, self.ptr)
+        self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """Owns a tsg_context (device, caching allocator, outputs of the last call)."""
 
     def __init__(self, device=0):
         self.ptr = C.c_void_p()
+        self._plans = weakref.WeakSet()
         check("tsg_context_create", lib().tsg_context_create(device, C.byref(self.ptr)))
         self.device = device
 
     def close(self):
         if self.ptr:
+            for p in list(self._plans):  # (tsg_context_destroy frees the plans still alive)
+                p.ptr = C.c_void_p()
             lib().tsg_context_destroy(self.ptr)
             self.ptr = C.c_void_p()
+
+    def numeric_plan(self, A, B, Cpattern, stream=None):
+        """A NumericPlan for C = A*B on the patterns of the DeviceCSRs A, B and
+        Cpattern (values ignored; C's columns strictly ascending per row and
+        containing A*B's pattern).  Raises TsgError (TSG_ERR_INVALID) for a
+        malformed pattern."""
+        p = NumericPlan(self, A, B, Cpattern, stream)
+        self._plans.add(p)
+        return p
 
     def __del__(self):
         try:

@@ -13,6 +13,7 @@ kernels of libtsg.so through the C ABI (include/tsg.h):
   tilespgemm(A, B, tm, tn, nnzCub)   -> (C, info)     tilespgemm-cuda.h:2220-2844
   tile2csr(C, tm, tn)                                  tile2csr.h:72-140
   spgemm(A, B, tm, tn)               -> (Matrix, stats)  one-shot CSR -> CSR
+  spgemm_numeric(A, B, C)            -> stats         values only, on C's known pattern
 
 Errors raise TsgError (the reference exits or silently misbehaves instead).
 """
@@ -27,6 +28,7 @@ _CSR_FIELDS = ("rowpointer", "columnindex", "value")
 
 # stats["path"]: the CSR-in -> CSR-out route that ran (include/tsg.h TSG_PATH_*)
 PATH_TILES, PATH_BAND, PATH_ROWS = 0, 2, 3  # (1: the retired fused path)
+PATH_NUMERIC = 4  # spgemm_numeric / NumericPlan.run
 
 
 def _view(ptr, n, dt):
@@ -155,6 +157,16 @@ def tilespgemm(A, B, tile_size_m=16, tile_size_n=16, nnzCub=0, filename=None):
 
 def tile2csr(Cm, tile_size_m=16, tile_size_n=16):
     check("tsg_tile2csr", lib().tsg_tile2csr(C.byref(Cm.s), tile_size_m, tile_size_n))
+
+
+def spgemm_numeric(A, B, Cm):
+    """Numeric-only product on a known pattern: Cm's rowpointer / columnindex
+    given (strictly ascending columns per row, containing A*B's pattern), Cm's
+    values overwritten with those of A*B.  Returns the stats dict."""
+    st = Stats()
+    check("tsg_spgemm_csr_numeric", lib().tsg_spgemm_csr_numeric(C.byref(A.s), C.byref(B.s), C.byref(Cm.s),
+                                                                 C.byref(st)))
+    return st.as_dict()
 
 
 def spgemm(A, B, tile_size_m=16, tile_size_n=16):

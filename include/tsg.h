@@ -111,13 +111,19 @@ int tsg_nnzcub(const tsg_smatrix *A, const tsg_smatrix *B, unsigned long long *n
 
 /* Replaces csr2tile_row_major (src/csr2tile.h:205).  Fills the tile fields of A
  * (tile_ptr, tile_columnidx, tile_rowidx, tile_nnz, tile_csr_Ptr [numtile*tm],
- * tile_csr_Col = r*tn+c, tile_csr_Value, mask). */
+ * tile_csr_Col = r*tn+c, tile_csr_Value, mask).  tile_rowidx[t] (numtile) is
+ * the tile row of tile t of the row-major list: i for tile_ptr[i] <= t <
+ * tile_ptr[i+1]. */
 int tsg_csr2tile_row_major(tsg_smatrix *A, int tile_size_m, int tile_size_n);
 
 /* Replaces csr2tile_col_major (src/csr2tile.h:279).  B tiles are tn x tm:
  * row-major structure (tile_ptr/tile_columnidx), CSC structure
  * (csc_tile_ptr/csc_tile_rowidx), payload in CSC tile order (tile_nnz,
- * tile_csr_Ptr [numtile*tn], tile_csr_Col = local col, tile_csr_Value, mask). */
+ * tile_csr_Ptr [numtile*tn], tile_csr_Col = local col, tile_csr_Value, mask).
+ * tile_rowidx (numtile) goes with the row-major structure as for A: the tile
+ * row of tile t of tile_ptr / tile_columnidx.  (The reference allocates B's
+ * tile_rowidx zero-filled and neither fills nor reads it, src/csr2tile.h:336-337;
+ * csc_tile_rowidx is the field its SpGEMM steps use.) */
 int tsg_csr2tile_col_major(tsg_smatrix *B, int tile_size_m, int tile_size_n);
 
 /* Replaces tilespgemm (src/tilespgemm-cuda.h:2220-2235), same argument list.
@@ -127,7 +133,10 @@ int tsg_csr2tile_col_major(tsg_smatrix *B, int tile_size_m, int tile_size_n);
  * exclusive [numblkC+1], tile_csr_Ptr [numblkC*tm], tile_csr_Col,
  * tile_csr_Value, mask) plus m, n, tilem, tilen, numtile, nnz.  Structurally
  * empty C tiles (step-1 tiles whose element product is empty) are kept with
- * nnz 0 and an all-zero Ptr, exactly the reference's C tile list.
+ * nnz 0, an all-zero Ptr and an all-zero mask, exactly the reference's C tile
+ * list.  C's mask (numblkC * tm * tm/16 words, which the reference leaves on the
+ * device) has the operands' layout: word c / 16 of row r, bit 15 - c % 16, set
+ * for every structural nonzero; tile_rowidx as for A.
  * filename is only echoed in the printed lines (may be NULL). */
 int tsg_tilespgemm(tsg_smatrix *A, tsg_smatrix *B, tsg_smatrix *C,
                    unsigned int *blk_intersec_bitmask_A, unsigned int *blk_intersec_bitmask_B,

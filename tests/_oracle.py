@@ -131,6 +131,7 @@ class OMat:
         d = dict(tilem=s.tilem, tilen=s.tilen, numtile=s.numtile,
                  tile_ptr=_arr(s.tile_ptr, s.tilem + 1, np.int32),
                  tile_columnidx=_arr(s.tile_columnidx, s.numtile, np.int32),
+                 tile_rowidx=_arr(s.tile_rowidx, s.numtile, np.int32),
                  tile_nnz=_arr(s.tile_nnz, s.numtile + 1, np.int32),
                  tile_csr_Ptr=_arr(s.tile_csr_Ptr, s.numtile * ptr_rows, np.uint16),
                  tile_csr_Col=_arr(s.tile_csr_Col, s.nnz if not csc else s.nnz, np.uint16),
@@ -176,6 +177,7 @@ def c_tiles(Cm, tm):
     return dict(tilem=s.tilem, tilen=s.tilen, numtile=s.numtile,
                 tile_ptr=_arr(s.tile_ptr, s.tilem + 1, np.int32),
                 tile_columnidx=_arr(s.tile_columnidx, s.numtile, np.int32),
+                tile_rowidx=_arr(s.tile_rowidx, s.numtile, np.int32),
                 tile_nnz=_arr(s.tile_nnz, s.numtile + 1, np.int32),
                 tile_csr_Ptr=_arr(s.tile_csr_Ptr, s.numtile * tm, np.uint16),
                 tile_csr_Col=_arr(s.tile_csr_Col, nnz, np.uint16),

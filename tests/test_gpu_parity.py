@@ -20,8 +20,7 @@ from spgemm_amd import tilespgemm as T
 pytestmark = pytest.mark.gpu
 RTOL = 1e-10
 TILE_KEYS = ("tile_ptr", "tile_columnidx", "tile_nnz", "tile_csr_Ptr", "tile_csr_Col", "tile_csr_Value", "mask")
-# C's masks are device-internal in the reference too (never copied back, src/tilespgemm-cuda.h:2749-2775)
-C_KEYS = TILE_KEYS[:-1]
+C_KEYS = TILE_KEYS  # C's masks are returned (zeroed for empty tiles) and compared
 SUPPORTED = {(16, 16), (32, 16), (32, 32), (48, 16), (16, 48), (48, 48), (64, 64), (64, 16)}  # all golden sizes
 
 
@@ -37,6 +36,23 @@ def both(path, aat):
     oA = O.OMat.load(path)
     oB = O.transpose(oA) if aat else O.OMat.alias(oA)
     return A, B, oA, oB
+
+
+def assert_rowidx(t, ot, who):
+    """tile_rowidx against the oracle's and against its definition: tile t of
+    the row-major list lies in the tile row whose tile_ptr range holds t (for B
+    too: include/tsg.h; the reference leaves B's array zero-filled and unread)."""
+    np.testing.assert_array_equal(t["tile_rowidx"], ot["tile_rowidx"], err_msg=who + " tile_rowidx")
+    want = np.repeat(np.arange(t["tilem"], dtype=np.int32), np.diff(t["tile_ptr"]))
+    np.testing.assert_array_equal(t["tile_rowidx"], want, err_msg=who + " tile_rowidx (definition)")
+
+
+def assert_c_tiles(ct, oct_, note=""):
+    """every array tsg_tilespgemm returns for C, bit-exact against the oracle's"""
+    assert ct["numtile"] == oct_["numtile"]
+    for k in C_KEYS:
+        np.testing.assert_array_equal(ct[k], oct_[k], err_msg=f"C {k} {note}")
+    assert_rowidx(ct, oct_, "C " + note)
 
 
 def assert_csr_equal(got, ref, values=True):
@@ -82,9 +98,9 @@ def test_pipeline_stages_vs_reference_goldens(path, name, aat, tm, tn):
     ct, oct_ = Cm.tiles(tm, tm // 16), O.c_tiles(oC, tm)
     np.testing.assert_array_equal(ct["tile_ptr"], g(ref, "Ct.tile_ptr"))
     np.testing.assert_array_equal(ct["tile_columnidx"], g(ref, "Ct.tile_columnidx"))
-    assert ct["numtile"] == oct_["numtile"]
-    for k in C_KEYS:
-        np.testing.assert_array_equal(ct[k], oct_[k], err_msg="C " + k)
+    assert_c_tiles(ct, oct_)
+    assert_rowidx(at, oA.tiles(tm, tn // 16), "A")
+    assert_rowidx(bt, oB.tiles(tn, tm // 16, csc=True), "B")
     assert info["nnzC"] == oC.s.nnz
     # GPU tile2csr vs the reference SPA pattern + oracle values
     T.tile2csr(Cm, tm, tm)
@@ -130,11 +146,12 @@ def test_random_matrices_tiled_and_csr(m, n, density, unsorted, dups):
     for k in TILE_KEYS:
         np.testing.assert_array_equal(at[k], oat[k], err_msg="A " + k)
         np.testing.assert_array_equal(bt[k], obt[k], err_msg="B " + k)
+    assert_rowidx(at, oat, "A")
+    assert_rowidx(bt, obt, "B")
     Cm, _ = T.tilespgemm(A, B, 16, 16)
     oC = O.tilespgemm(oA, oB, 16, 16)
     ct, oct_ = Cm.tiles(16, 1), O.c_tiles(oC, 16)
-    for k in C_KEYS:
-        np.testing.assert_array_equal(ct[k], oct_[k], err_msg="C " + k)
+    assert_c_tiles(ct, oct_)
     T.tile2csr(Cm, 16, 16)
     ref = O.gustavson(oA, oB)
     assert_csr_equal(Cm.csr(), ref.csr())
@@ -315,11 +332,12 @@ def test_other_tile_sizes_vs_oracle(tm, tn, aat):
     for k in TILE_KEYS:
         np.testing.assert_array_equal(at[k], oat[k], err_msg="A " + k)
         np.testing.assert_array_equal(bt[k], obt[k], err_msg="B " + k)
+    assert_rowidx(at, oat, "A")
+    assert_rowidx(bt, obt, "B")
     Cm, _ = T.tilespgemm(A, B, tm, tn)
     oC = O.tilespgemm(oA, oB, tm, tn)
     ct, oct_ = Cm.tiles(tm, tm // 16), O.c_tiles(oC, tm)
-    for k in C_KEYS:
-        np.testing.assert_array_equal(ct[k], oct_[k], err_msg="C " + k)
+    assert_c_tiles(ct, oct_)
     T.tile2csr(Cm, tm, tm)
     assert_csr_equal(Cm.csr(), O.gustavson(oA, oB).csr())
 
@@ -343,8 +361,9 @@ def test_dense_accumulator_tiles(tm, tn):
     oC = O.tilespgemm(oA, oB, tm, tn)
     ct, oct_ = Cm.tiles(tm, tm // 16), O.c_tiles(oC, tm)
     assert np.diff(ct["tile_nnz"]).max() > 512  # the dense accumulator ran
-    for k in C_KEYS:
-        np.testing.assert_array_equal(ct[k], oct_[k], err_msg="C " + k)
+    assert_c_tiles(ct, oct_)
+    assert_rowidx(A.tiles(tm, tn // 16), oA.tiles(tm, tn // 16), "A")
+    assert_rowidx(B.tiles(tn, tm // 16, csc=True), oB.tiles(tn, tm // 16, csc=True), "B")
     assert info["time_step2"] > 0 and info["time_step3"] > 0
     T.tile2csr(Cm, tm, tm)
     assert_csr_equal(Cm.csr(), O.gustavson(oA, oB).csr())
@@ -376,6 +395,8 @@ def test_tiled_api_csr_streaming_and_tile_payload_agree(path, name, aat, tm, tn,
         O.csr2tile_row_major(oA, tm, tn)
         O.csr2tile_col_major(oB, tm, tn)
         oct_ = O.c_tiles(O.tilespgemm(oA, oB, tm, tn), tm)
+        assert_rowidx(A.tiles(tm, tn // 16), oA.tiles(tm, tn // 16), "A")
+        assert_rowidx(B.tiles(tn, tm // 16, csc=True), oB.tiles(tn, tm // 16, csc=True), "B")
         for mode in (None, "0"):
             if mode is None:
                 monkeypatch.delenv("TSG_TILED_CSR", raising=False)
@@ -384,8 +405,7 @@ def test_tiled_api_csr_streaming_and_tile_payload_agree(path, name, aat, tm, tn,
             Cm, info = T.tilespgemm(A, B, tm, tn, nnzCub=int(g(ref, "nnzCub")))
             ct = Cm.tiles(tm, tm // 16)
             np.testing.assert_array_equal(ct["tile_ptr"], g(ref, "Ct.tile_ptr"))
-            for k in C_KEYS:
-                np.testing.assert_array_equal(ct[k], oct_[k], err_msg=f"C {k} (sorted={srt}, mode={mode})")
+            assert_c_tiles(ct, oct_, f"(sorted={srt}, mode={mode})")
             del Cm
 
 
@@ -412,7 +432,7 @@ def test_tiled_api_csr_streaming_real_values():
 
 def test_tiled_csr_route_wide_tile_rows_and_empty_tiles():
     """The 16x16 tiled route through the CSR C (tsg_ctiles.hip): one tile row
-    spanning ~20 units of <= 992 tiles (B's row 0 reaches 20,000 tile columns),
+    spanning ~40 units of <= 496 tiles (CT_TC; B's row 0 reaches 20,000 tile columns),
     several rows of the tile row in the same tiles (multi-row masks and Ptr),
     and step-1 tiles whose element product is empty (A's column 1 selects an
     empty B row inside a tile pair that the tile pattern matches).  Every C
@@ -448,13 +468,112 @@ def test_tiled_csr_route_wide_tile_rows_and_empty_tiles():
     Cm, info = T.tilespgemm(A, B, 16, 16)
     oC = O.tilespgemm(oA, oB, 16, 16)
     ct, oct_ = Cm.tiles(16, 1), O.c_tiles(oC, 16)
-    for k in C_KEYS:
-        np.testing.assert_array_equal(ct[k], oct_[k], err_msg="C " + k)
-    assert int(ct["tile_ptr"][1]) > 5 * 992  # the first tile row spans several units
+    assert_c_tiles(ct, oct_)
+    assert_rowidx(A.tiles(16, 1), oA.tiles(16, 1), "A")
+    assert_rowidx(B.tiles(16, 1, csc=True), oB.tiles(16, 1, csc=True), "B")
+    assert int(ct["tile_ptr"][1]) > 10 * CT_TC  # the first tile row spans several units
     tn = np.diff(ct["tile_nnz"][: len(ct["tile_columnidx"]) + 1])
     assert (tn == 0).any()  # structurally present, numerically empty tiles
     T.tile2csr(Cm, 16, 16)
     assert_csr_equal(Cm.csr(), O.gustavson(oA, oB).csr())
+
+
+CT_TC, CT_EB = 496, 1024  # tsg_ctiles.hip: tiles per unit; nonzeros per register batch (CT_EPT * CT_NT)
+
+
+def _ctiles_edge_operands():
+    """A (53 x 64) and B (64 x n) whose C has tile rows of 496, 497, 992 and 993
+    step-1 tiles (B's tile row i feeds C's tile row i alone).  In tile row i the
+    rows 16i and 16i+3 select B row 16i (one column in every non-empty tile),
+    row 16i+3 also B row 16i+1 (`extra` more columns, some of them B row 16i's:
+    two-term sums), row 16i+4 B rows 16i+1 and 16i+3 (empty); tile row 2 has a
+    third full row.  B row 16i+2, which no A entry selects, alone holds every
+    31st tile column: a step-1 tile without a nonzero."""
+    rng = np.random.default_rng(496)
+    counts = (CT_TC, CT_TC + 1, 2 * CT_TC, 2 * CT_TC + 1)
+    extras = {0: (34, 4), 1: (35, 5), 2: (200, 9), 3: (61, 3)}  # (columns of B row 16i+1, of them shared with row 16i)
+    arows = [[] for _ in range(53)]
+    brows = [np.zeros(0, np.int64) for _ in range(64)]
+    for i, nt_ in enumerate(counts):
+        tc = 2 * np.arange(nt_) + i % 2  # the tile row's tile columns
+        hollow = np.arange(nt_) % 31 == 5
+        full = tc[~hollow]
+        base = 16 * full + full % 16
+        brows[16 * i] = base
+        ne, nshared = extras[i]
+        q = np.arange(ne - nshared)
+        more = 16 * full[q // 4] + (full[q // 4] % 16 + 1 + 3 * (q % 4)) % 16
+        if i == 3:  # the one-tile unit at the end: several rows and columns
+            more = np.concatenate([more, 16 * tc[-1] + (tc[-1] % 16 + np.array([2, 5, 9])) % 16])
+        brows[16 * i + 1] = np.sort(np.concatenate([base[:nshared], more]))
+        brows[16 * i + 2] = 16 * tc[hollow] + 7
+        arows[16 * i] = [16 * i]
+        arows[16 * i + 3] = [16 * i, 16 * i + 1]
+        arows[16 * i + 4] = [16 * i + 1, 16 * i + 3]
+        if i == 2:
+            arows[16 * i + 7] = [16 * i]
+    n = 16 * (2 * counts[-1] + 2)
+    lens = [len(r) for r in arows]
+    arp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    aci = np.concatenate([np.array(r, np.int32) for r in arows]).astype(np.int32)
+    brp = np.concatenate([[0], np.cumsum([len(r) for r in brows])]).astype(np.int32)
+    bci = np.concatenate(brows).astype(np.int32)
+    return (53, 64, arp, aci, rng.uniform(-1, 1, len(aci))), (64, n, brp, bci, rng.uniform(-1, 1, len(bci))), counts
+
+
+@pytest.mark.parametrize("mode", [None, "0"])
+def test_tiled_route_at_the_unit_edges(mode, monkeypatch):
+    """k_ctiles at its unit edges (and, with TSG_TILED_CSR=0, the staged steps 2
+    and 3 on the same product): tile rows of exactly CT_TC, CT_TC + 1, 2 CT_TC
+    and 2 CT_TC + 1 step-1 tiles -- one unit, one unit and a one-tile unit, two
+    full units, two and a one-tile unit; units of exactly CT_EB and CT_EB + 1
+    nonzeros (one register batch, two); tiles holding several rows; a last tile
+    row of 5 rows (m = 53); step-1 tiles without a nonzero; real values.  The
+    counts are taken from the oracle's C.  Every C field bit-exact against the
+    oracle (values within 1e-10 of |A|*|B|), the CSR after tile2csr against
+    Gustavson."""
+    if mode is None:
+        monkeypatch.delenv("TSG_TILED_CSR", raising=False)
+    else:
+        monkeypatch.setenv("TSG_TILED_CSR", mode)
+    (m, k, arp, aci, avv), (_, n, brp, bci, bvv), counts = _ctiles_edge_operands()
+    A, B = T.Matrix.from_csr(m, k, arp, aci, avv), T.Matrix.from_csr(k, n, brp, bci, bvv)
+    oA, oB = O.OMat.from_csr(m, k, arp, aci, avv), O.OMat.from_csr(k, n, brp, bci, bvv)
+    oAm, oBm = O.OMat.from_csr(m, k, arp, aci, np.abs(avv)), O.OMat.from_csr(k, n, brp, bci, np.abs(bvv))
+    T.csr2tile_row_major(A, 16, 16)
+    T.csr2tile_col_major(B, 16, 16)
+    for a, b in ((oA, oB), (oAm, oBm)):
+        O.csr2tile_row_major(a, 16, 16)
+        O.csr2tile_col_major(b, 16, 16)
+    oC = O.tilespgemm(oA, oB, 16, 16)
+    oct_, mag = O.c_tiles(oC, 16), O.c_tiles(O.tilespgemm(oAm, oBm, 16, 16), 16)
+    # where the product sits, from the oracle's C
+    tp, tnz = oct_["tile_ptr"], np.diff(oct_["tile_nnz"])
+    assert m % 16 == 5 and np.diff(tp).tolist() == list(counts)
+    unit_nnz = [int(tnz[c:min(c + CT_TC, tp[i + 1])].sum()) for i in range(len(tp) - 1)
+                for c in range(tp[i], tp[i + 1], CT_TC)]
+    unit_tiles = [min(c + CT_TC, tp[i + 1]) - c for i in range(len(tp) - 1) for c in range(tp[i], tp[i + 1], CT_TC)]
+    assert unit_tiles == [CT_TC, CT_TC, 1, CT_TC, CT_TC, CT_TC, CT_TC, 1]
+    assert unit_nnz[0] == CT_EB and unit_nnz[1] == CT_EB + 1 and max(unit_nnz) > CT_EB + 256
+    assert (tnz == 0).sum() >= 16 * 6  # step-1 tiles without a nonzero, in every full unit
+    ptr = oct_["tile_csr_Ptr"].reshape(-1, 16)
+    rows_in_tile = (np.diff(np.concatenate([ptr, tnz[:, None]], axis=1).astype(np.int64), axis=1) > 0).sum(axis=1)
+    assert rows_in_tile.max() >= 3 and rows_in_tile[-1] >= 2  # tiles holding several rows (the one-tile unit too)
+    Cm, info = T.tilespgemm(A, B, 16, 16)
+    ct = Cm.tiles(16, 1)
+    assert ct["numtile"] == oct_["numtile"]
+    for key in C_KEYS:
+        if key != "tile_csr_Value":
+            np.testing.assert_array_equal(ct[key], oct_[key], err_msg="C " + key)
+    assert_rowidx(ct, oct_, "C")
+    assert np.all(np.abs(ct["tile_csr_Value"] - oct_["tile_csr_Value"]) <= RTOL * mag["tile_csr_Value"])
+    assert info["nnzC"] == oC.s.nnz
+    T.tile2csr(Cm, 16, 16)
+    got, ref = Cm.csr(), O.gustavson(oA, oB).csr()
+    gmag = O.gustavson(oAm, oBm).csr()[4]
+    np.testing.assert_array_equal(got[2], ref[2])
+    np.testing.assert_array_equal(got[3], ref[3])
+    assert np.all(np.abs(got[4] - ref[4]) <= RTOL * gmag)
 
 
 @pytest.mark.parametrize("which", ["A", "B"])
@@ -488,8 +607,7 @@ def test_tiled_csr_disagreeing_with_tiles_takes_the_payload_route(which):
     M.s.value = vv2.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
     Cm, _ = T.tilespgemm(A, B, 16, 16)
     ct = Cm.tiles(16, 1)
-    for k in C_KEYS:
-        np.testing.assert_array_equal(ct[k], want[k], err_msg=f"C {k} ({which}'s CSR disagrees)")
+    assert_c_tiles(ct, want, f"({which}'s CSR disagrees)")
     T.tile2csr(Cm, 16, 16)
     assert_csr_equal(Cm.csr(), O.gustavson(oA, oB).csr())
 
@@ -534,8 +652,7 @@ def test_tiled_csr_with_other_columns_reruns_on_the_payload_route():
     A.s.columnindex = ci2.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
     Cm, _ = T.tilespgemm(A, B, 16, 16)
     ct = Cm.tiles(16, 1)
-    for k in C_KEYS:
-        np.testing.assert_array_equal(ct[k], want[k], err_msg=f"C {k}")
+    assert_c_tiles(ct, want)
     T.tile2csr(Cm, 16, 16)
     assert_csr_equal(Cm.csr(), O.gustavson(oA, oB).csr())
 

@@ -108,5 +108,6 @@ def test_wide_b_tile_mode_step1_vs_oracle(nb):
     oC = O.tilespgemm(oA, oB, 16, 16)
     ct, oct_ = Cm.tiles(16, 1), O.c_tiles(oC, 16)
     assert ct["numtile"] == oct_["numtile"]
-    for key in ("tile_ptr", "tile_columnidx", "tile_nnz", "tile_csr_Ptr", "tile_csr_Col", "tile_csr_Value"):
+    for key in ("tile_ptr", "tile_columnidx", "tile_nnz", "tile_csr_Ptr", "tile_csr_Col", "tile_csr_Value",
+                "mask"):
         np.testing.assert_array_equal(ct[key], oct_[key], err_msg=key)

@@ -10,7 +10,8 @@ block.  Compared, as the reference's own end-of-run check does for the whole
 C (src/main.cu:325-350), but field by field:
 
   * C's tile structure (tile_ptr, tile_columnidx, empty tiles included) and
-    every C tile field (tile_nnz, tile_csr_Ptr, tile_csr_Col, tile_csr_Value)
+    every C tile field (tile_nnz, tile_csr_Ptr, tile_csr_Col, tile_csr_Value,
+    mask)
     against the oracle's tiled product (tests/_oracle.py tilespgemm, pinned to
     the reference's host code by tests/test_oracle.py); integer fields
     bit-exact, values within rtol 1e-10 (exact in practice: value = pos % 10);
@@ -26,7 +27,7 @@ from spgemm_amd import tilespgemm as T
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-10
-C_FIELDS = ("tile_nnz", "tile_csr_Ptr", "tile_csr_Col")
+C_FIELDS = ("tile_nnz", "tile_csr_Ptr", "tile_csr_Col", "mask")
 
 
 def _operands(m, n, rp, ci, vv, aat, B_csr=None):

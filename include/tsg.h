@@ -205,12 +205,36 @@ typedef struct tsg_dev_tiles {
 } tsg_dev_tiles;
 
 /* A context owns a device, a caching device allocator and the outputs of the
- * tsg_dev_* calls made on it.  One stream per call; not thread-safe per context. */
+ * tsg_dev_* calls made on it.  One stream per call; not thread-safe per context.
+ *
+ * Error contract of the tsg_dev_* calls: a call that returns an error has
+ * drained its stream, has returned every block it took from the context's
+ * allocator to the cache (temporaries and half-built outputs alike), and has
+ * zeroed its output struct (*plan = NULL for a numeric plan).  Blocks of
+ * earlier calls -- their outputs -- are untouched, and the context stays usable:
+ * the same call can simply be made again.  A call that succeeds leaves only its
+ * outputs allocated, and synchronises no more than it documents. */
 int tsg_context_create(int device, tsg_context **ctx);
 int tsg_context_destroy(tsg_context *ctx);
 /* Returns every context-owned output/temporary block to the cache (numeric
  * plans keep their memory: it is not the cache's). */
 int tsg_context_reset(tsg_context *ctx);
+
+/* ---- diagnostics ----
+ * The caching allocator's counters, and a one-shot allocation failure, so that
+ * the error contract of the tsg_dev_* calls can be tested. */
+typedef struct tsg_pool_stats {
+    long long live_blocks;    /* blocks handed out and not yet returned to the cache */
+    long long live_bytes;     /* their size classes' bytes                           */
+    long long reserved_bytes; /* device memory held: live + cached                   */
+    long long allocs;         /* pool allocations since the context was created      */
+} tsg_pool_stats;
+int tsg_context_pool_stats(tsg_context *ctx, tsg_pool_stats *out);
+/* The nth pool allocation from now (0 = the next) returns TSG_ERR_OOM once,
+ * without calling hipMalloc; nth < 0 clears a pending injection.  Returns 1
+ * if an injection was still pending when this call was made (it had not
+ * fired), else 0; TSG_ERR_INVALID for a NULL ctx.  A host-side counter in the allocator, nothing more. */
+int tsg_context_fail_alloc(tsg_context *ctx, long long nth);
 
 int tsg_dev_csr2tile_row_major(tsg_context *ctx, const tsg_dev_csr *A, int tile_size_m,
                                int tile_size_n, void *stream, tsg_dev_tiles *out);

@@ -80,6 +80,14 @@ class NumericInfo(C.Structure):
                     split_units=self.split_units, b_rows_sorted=self.b_rows_sorted)
 
 
+class PoolStats(C.Structure):
+    """tsg_pool_stats, field for field."""
+    _fields_ = [(n, C.c_longlong) for n in ("live_blocks", "live_bytes", "reserved_bytes", "allocs")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 _lib = None
 
 _SIGS = {
@@ -105,6 +113,8 @@ _SIGS = {
     "tsg_context_create": ([C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "tsg_context_destroy": ([C.c_void_p], C.c_int),
     "tsg_context_reset": ([C.c_void_p], C.c_int),
+    "tsg_context_pool_stats": ([C.c_void_p, C.POINTER(PoolStats)], C.c_int),
+    "tsg_context_fail_alloc": ([C.c_void_p, C.c_longlong], C.c_int),
     "tsg_dev_csr2tile_row_major": ([C.c_void_p, C.POINTER(DevCSR), C.c_int, C.c_int, C.c_void_p,
                                     C.POINTER(DevTiles)], C.c_int),
     "tsg_dev_csr2tile_col_major": ([C.c_void_p, C.POINTER(DevCSR), C.c_int, C.c_int, C.c_void_p,

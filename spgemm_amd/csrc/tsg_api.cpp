@@ -7,6 +7,7 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cctype>
 #include <chrono>
 #include <cstdio>
@@ -40,6 +41,11 @@ DevicePool::~DevicePool() { trim(); }
 
 int DevicePool::alloc(void **p, size_t bytes) {
     size_t c = size_class(bytes ? bytes : 1);
+    ++allocs_;
+    if (fail_in_ >= 0 && fail_in_-- == 0) {  // (the injected failure: once)
+        *p = nullptr;
+        return TSG_ERR_OOM;
+    }
     auto it = free_.find(c);
     if (it != free_.end()) {
         *p = it->second;
@@ -70,6 +76,15 @@ void DevicePool::release(void *p) {
     if (it == live_.end()) return;
     free_.emplace(it->second, p);
     live_.erase(it);
+}
+
+tsg_pool_stats DevicePool::stats() const {
+    tsg_pool_stats st{};
+    st.live_blocks = (long long)live_.size();
+    for (auto &kv : live_) st.live_bytes += (long long)kv.second;
+    st.reserved_bytes = (long long)reserved_;
+    st.allocs = allocs_;
+    return st;
 }
 
 void DevicePool::release_all_live() {
@@ -232,8 +247,8 @@ class HostLease {
     tsg_context *c_ = nullptr;
 };
 
-template <class T> static int upload(Context &cx, T **d, const T *h, size_t n, hipStream_t s) {
-    TSG_TRY(cx.get(d, n ? n : 1));
+template <class T> static int upload(PoolScope &ws, T **d, const T *h, size_t n, hipStream_t s) {
+    TSG_TRY(ws.get(d, n ? n : 1));
     if (n) TSG_HIP(hipMemcpyAsync(*d, h, n * sizeof(T), hipMemcpyHostToDevice, s));
     return TSG_OK;
 }
@@ -249,13 +264,13 @@ static bool valid_tiles(int tm, int tn) {
     return tm > 0 && tn > 0 && tm % 16 == 0 && tn % 16 == 0 && tm <= 64 && tn <= 64 && (long)tm * tn <= 65536;
 }
 
-static int upload_csr(Context &cx, const tsg_smatrix *A, tsg_dev_csr &d, hipStream_t s) {
+static int upload_csr(PoolScope &ws, const tsg_smatrix *A, tsg_dev_csr &d, hipStream_t s) {
     d.m = A->m;
     d.n = A->n;
     d.nnz = A->nnz;
-    TSG_TRY(upload(cx, &d.rowpointer, A->rowpointer, (size_t)A->m + 1, s));
-    TSG_TRY(upload(cx, &d.columnindex, A->columnindex, (size_t)A->nnz, s));
-    TSG_TRY(upload(cx, &d.value, A->value, (size_t)A->nnz, s));
+    TSG_TRY(upload(ws, &d.rowpointer, A->rowpointer, (size_t)A->m + 1, s));
+    TSG_TRY(upload(ws, &d.columnindex, A->columnindex, (size_t)A->nnz, s));
+    TSG_TRY(upload(ws, &d.value, A->value, (size_t)A->nnz, s));
     return TSG_OK;
 }
 
@@ -292,36 +307,39 @@ static int download_tiles(const tsg_dev_tiles &t, tsg_smatrix *M, bool csc, hipS
 }
 
 // the tile structure alone (tile_ptr, tile_columnidx): what step 1 reads
-static int upload_tile_structure(Context &cx, const tsg_smatrix *M, int tile_m, int tile_n, tsg_dev_tiles &t,
+static int upload_tile_structure(PoolScope &ws, const tsg_smatrix *M, int tile_m, int tile_n, tsg_dev_tiles &t,
                                  hipStream_t s) {
     t = tsg_dev_tiles{};
     t.m = M->m; t.n = M->n; t.nnz = M->nnz;
     t.tile_m = tile_m; t.tile_n = tile_n;
     t.tilem = M->tilem; t.tilen = M->tilen; t.numtile = M->numtile;
-    TSG_TRY(upload(cx, &t.tile_ptr, M->tile_ptr, (size_t)M->tilem + 1, s));
-    TSG_TRY(upload(cx, &t.tile_columnidx, M->tile_columnidx, (size_t)M->numtile, s));
+    TSG_TRY(upload(ws, &t.tile_ptr, M->tile_ptr, (size_t)M->tilem + 1, s));
+    TSG_TRY(upload(ws, &t.tile_columnidx, M->tile_columnidx, (size_t)M->numtile, s));
     return TSG_OK;
 }
 
-static int upload_tiles(Context &cx, const tsg_smatrix *M, int tile_m, int tile_n, bool csc, tsg_dev_tiles &t,
+static int upload_tiles(Context &cx, PoolScope &ws, const tsg_smatrix *M, int tile_m, int tile_n, bool csc, tsg_dev_tiles &t,
                         hipStream_t s) {
     t = tsg_dev_tiles{};
     t.m = M->m; t.n = M->n; t.nnz = M->nnz;
     t.tile_m = tile_m; t.tile_n = tile_n;
     t.tilem = M->tilem; t.tilen = M->tilen; t.numtile = M->numtile;
     const size_t nt = (size_t)M->numtile;
-    TSG_TRY(upload(cx, &t.tile_ptr, M->tile_ptr, (size_t)M->tilem + 1, s));
-    TSG_TRY(upload(cx, &t.tile_columnidx, M->tile_columnidx, nt, s));
-    TSG_TRY(upload(cx, &t.tile_nnz, M->tile_nnz, nt + 1, s));
-    TSG_TRY(upload(cx, &t.tile_csr_Ptr, M->tile_csr_Ptr, nt * tile_m, s));
-    TSG_TRY(upload(cx, &t.tile_csr_Col, M->tile_csr_Col, (size_t)M->nnz, s));
-    TSG_TRY(upload(cx, &t.tile_csr_Value, M->tile_csr_Value, (size_t)M->nnz, s));
-    if (M->mask) TSG_TRY(upload(cx, &t.mask, M->mask, nt * tile_m * (tile_n / 16), s));
+    TSG_TRY(upload(ws, &t.tile_ptr, M->tile_ptr, (size_t)M->tilem + 1, s));
+    TSG_TRY(upload(ws, &t.tile_columnidx, M->tile_columnidx, nt, s));
+    TSG_TRY(upload(ws, &t.tile_nnz, M->tile_nnz, nt + 1, s));
+    TSG_TRY(upload(ws, &t.tile_csr_Ptr, M->tile_csr_Ptr, nt * tile_m, s));
+    TSG_TRY(upload(ws, &t.tile_csr_Col, M->tile_csr_Col, (size_t)M->nnz, s));
+    TSG_TRY(upload(ws, &t.tile_csr_Value, M->tile_csr_Value, (size_t)M->nnz, s));
+    if (M->mask) TSG_TRY(upload(ws, &t.mask, M->mask, nt * tile_m * (tile_n / 16), s));
     if (csc) {
         if (!M->csc_tile_ptr || !M->csc_tile_rowidx) return TSG_ERR_INVALID;
-        TSG_TRY(upload(cx, &t.csc_tile_ptr, M->csc_tile_ptr, (size_t)M->tilen + 1, s));
-        TSG_TRY(upload(cx, &t.csc_tile_rowidx, M->csc_tile_rowidx, nt, s));
+        TSG_TRY(upload(ws, &t.csc_tile_ptr, M->csc_tile_ptr, (size_t)M->tilen + 1, s));
+        TSG_TRY(upload(ws, &t.csc_tile_rowidx, M->csc_tile_rowidx, nt, s));
         TSG_TRY(dev_rm2csc_from_structs(cx, t, s));
+        ws.adopt(t.tile_rm2csc);  // (the three views it added)
+        ws.adopt(t.rm_mask);
+        ws.adopt(t.rm_rowstart);
     }
     return TSG_OK;
 }
@@ -331,6 +349,40 @@ static int upload_tiles(Context &cx, const tsg_smatrix *M, int tile_m, int tile_
 static constexpr double kStep2ElemMaxTileDensity = 16.0;
 
 static bool quiet() { return getenv("TSG_QUIET") != nullptr; }
+
+// The run-time knobs, read here and nowhere else, at the top of each C-ABI call
+// that routes or times -- per call, not per process: tests switch them inside
+// one process.  (TSG_ABLATE alone is read once per process, tsg_device.hip.)
+static void read_knobs(Context &cx) {
+    auto is = [](const char *v, const char *w) { return v && !strcmp(v, w); };
+    const char *path = getenv("TSG_PATH"), *md = getenv("TSG_STEP2_MODE"), *se = getenv("TSG_STAGE_EVENTS");
+    const char *cs = getenv("TSG_ROWS_CHECKED_SCAN");
+    Knobs k;
+    k.force_path = is(path, "tiles") ? TSG_PATH_TILES : is(path, "band") ? TSG_PATH_BAND
+                   : is(path, "rows") ? TSG_PATH_ROWS : -1;
+    k.step2_mode = is(md, "elem") ? 1 : is(md, "tile") ? 0 : -1;
+    k.tiled_csr = !is(getenv("TSG_TILED_CSR"), "0");
+    k.rows_checked_scan = cs && cs[0] == '1';
+    k.dr_per_row = getenv("TSG_DR_PER_ROW") != nullptr;
+    cx.knobs = k;
+    cx.stage_ev = se && se[0] == '1';
+    // (the test-only knobs change what is timed: say so once, a silent A/B skew otherwise)
+    static std::atomic_flag told = ATOMIC_FLAG_INIT;
+    if ((k.rows_checked_scan || k.dr_per_row) && !quiet() && !told.test_and_set())
+        fprintf(stderr, "[tsg] TSG_ROWS_CHECKED_SCAN / TSG_DR_PER_ROW set: test-only row-merge paths, "
+                        "not the production timings\n");
+}
+// The error contract of the tsg_dev_* calls (include/tsg.h): on an error the
+// stream is drained and the output zeroed; the callee's scopes have returned
+// every block the call allocated.  The success path gains no synchronisation.
+template <class Out> static int dev_result(int rc, void *stream, Out *out) {
+    if (rc != TSG_OK) {
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) (void)hipGetLastError();
+        *out = Out{};
+    }
+    return rc;
+}
+
 // b_sorted: 1 = the caller already checked B's rows column-sorted (the check
 // is skipped), -1 = unknown (checked here)
 static int dev_spgemm16(Context &cx, const tsg_dev_csr *A, const tsg_dev_csr *B, hipStream_t s, tsg_dev_csr *C,
@@ -609,8 +661,9 @@ int tsg_transpose(const tsg_smatrix *A, tsg_smatrix *B) {
     TSG_TRY(lease.acquire());
     Context &cx = lease.cx();
     hipStream_t s = lease.stream();
+    PoolScope ws(cx);  // (the uploads; what the dev_* calls keep returns with the lease)
     tsg_dev_csr dA, dB;
-    TSG_TRY(upload_csr(cx, A, dA, s));
+    TSG_TRY(upload_csr(ws, A, dA, s));
     TSG_TRY(dev_transpose(cx, dA, dB, s));
     memset(B, 0, sizeof(*B));
     B->m = dB.m; B->n = dB.n; B->nnz = dB.nnz;
@@ -618,7 +671,6 @@ int tsg_transpose(const tsg_smatrix *A, tsg_smatrix *B) {
     TSG_TRY(download(&B->columnindex, dB.columnindex, (size_t)dB.nnz, s));
     TSG_TRY(download(&B->value, dB.value, (size_t)dB.nnz, s));
     TSG_HIP(hipStreamSynchronize(s));
-    cx.pool.release_all_live();
     return TSG_OK;
 }
 
@@ -628,15 +680,15 @@ int tsg_nnzcub(const tsg_smatrix *A, const tsg_smatrix *B, unsigned long long *o
     TSG_TRY(lease.acquire());
     Context &cx = lease.cx();
     hipStream_t s = lease.stream();
+    PoolScope ws(cx);  // (the uploads; what the dev_* calls keep returns with the lease)
     tsg_dev_csr dA, dB;
-    TSG_TRY(upload_csr(cx, A, dA, s));
-    TSG_TRY(upload(cx, &dB.rowpointer, B->rowpointer, (size_t)B->m + 1, s));
+    TSG_TRY(upload_csr(ws, A, dA, s));
+    TSG_TRY(upload(ws, &dB.rowpointer, B->rowpointer, (size_t)B->m + 1, s));
     unsigned long long *d = nullptr;
-    TSG_TRY(cx.get(&d, 1));
+    TSG_TRY(ws.get(&d, 1));
     TSG_TRY(launch_nnzcub(cx, dA, dB, d, s));
     TSG_HIP(hipMemcpyAsync(out, d, sizeof(*out), hipMemcpyDeviceToHost, s));
     TSG_HIP(hipStreamSynchronize(s));
-    cx.pool.release_all_live();
     return TSG_OK;
 }
 
@@ -647,12 +699,12 @@ int tsg_csr2tile_row_major(tsg_smatrix *A, int tm, int tn) {
     TSG_TRY(lease.acquire());
     Context &cx = lease.cx();
     hipStream_t s = lease.stream();
+    PoolScope ws(cx);  // (the uploads; what the dev_* calls keep returns with the lease)
     tsg_dev_csr d;
     tsg_dev_tiles t;
-    TSG_TRY(upload_csr(cx, A, d, s));
+    TSG_TRY(upload_csr(ws, A, d, s));
     int rc = dev_csr2tile_row_major(cx, d, tm, tn, t, s);
     if (rc == TSG_OK) rc = download_tiles(t, A, false, s);
-    cx.pool.release_all_live();
     return rc;
 }
 
@@ -663,12 +715,12 @@ int tsg_csr2tile_col_major(tsg_smatrix *B, int tm, int tn) {
     TSG_TRY(lease.acquire());
     Context &cx = lease.cx();
     hipStream_t s = lease.stream();
+    PoolScope ws(cx);  // (the uploads; what the dev_* calls keep returns with the lease)
     tsg_dev_csr d;
     tsg_dev_tiles t;
-    TSG_TRY(upload_csr(cx, B, d, s));
+    TSG_TRY(upload_csr(ws, B, d, s));
     int rc = dev_csr2tile_col_major(cx, d, tm, tn, t, s);
     if (rc == TSG_OK) rc = download_tiles(t, B, true, s);
-    cx.pool.release_all_live();
     return rc;
 }
 
@@ -689,6 +741,8 @@ int tsg_tilespgemm(tsg_smatrix *A, tsg_smatrix *B, tsg_smatrix *C, unsigned int 
     TSG_TRY(lease.acquire());
     Context &cx = lease.cx();
     hipStream_t s = lease.stream();
+    PoolScope ws(cx);  // (the uploads; what the dev_* calls keep returns with the lease)
+    read_knobs(cx);
     tsg_dev_tiles dA, dB, dC;
     // The reference's SMatrix carries the CSR beside the tiles (src/main.cu builds
     // both).  When both operands have it and B's rows are column-sorted, C comes
@@ -698,21 +752,17 @@ int tsg_tilespgemm(tsg_smatrix *A, tsg_smatrix *B, tsg_smatrix *C, unsigned int 
     // region, as in the reference.  TSG_TILED_CSR=0 keeps the tile-payload kernels.
     tsg_dev_csr cA{}, cB{};
     bool use_csr = false, bsorted = false;
-    {
-        const char *e = getenv("TSG_TILED_CSR");
-        const bool allow = !(e && !strcmp(e, "0"));
-        if (sq16 && allow && csr_matches_tiles(A, B, tm)) {
-            TSG_TRY(upload_csr(cx, A, cA, s));
-            TSG_TRY(upload_csr(cx, B, cB, s));
-            use_csr = true;  // (if B's rows turn out column-sorted: checked inside the timed region)
-        }
+    if (sq16 && cx.knobs.tiled_csr && csr_matches_tiles(A, B, tm)) {
+        TSG_TRY(upload_csr(ws, A, cA, s));
+        TSG_TRY(upload_csr(ws, B, cB, s));
+        use_csr = true;  // (if B's rows turn out column-sorted: checked inside the timed region)
     }
     if (use_csr) {
-        TSG_TRY(upload_tile_structure(cx, A, tm, tn, dA, s));
-        TSG_TRY(upload_tile_structure(cx, B, tn, tm, dB, s));
+        TSG_TRY(upload_tile_structure(ws, A, tm, tn, dA, s));
+        TSG_TRY(upload_tile_structure(ws, B, tn, tm, dB, s));
     } else {
-        TSG_TRY(upload_tiles(cx, A, tm, tn, false, dA, s));
-        TSG_TRY(upload_tiles(cx, B, tn, tm, true, dB, s));
+        TSG_TRY(upload_tiles(cx, ws, A, tm, tn, false, dA, s));
+        TSG_TRY(upload_tiles(cx, ws, B, tn, tm, true, dB, s));
     }
     TSG_HIP(hipStreamSynchronize(s));
     tsg_stats st{};
@@ -725,8 +775,8 @@ int tsg_tilespgemm(tsg_smatrix *A, tsg_smatrix *B, tsg_smatrix *C, unsigned int 
         TSG_TRY(dev_rows_sorted(cx, cB, &bsorted, s));
         use_csr = bsorted;
         if (!use_csr) {
-            TSG_TRY(upload_tiles(cx, A, tm, tn, false, dA, s));
-            TSG_TRY(upload_tiles(cx, B, tn, tm, true, dB, s));
+            TSG_TRY(upload_tiles(cx, ws, A, tm, tn, false, dA, s));
+            TSG_TRY(upload_tiles(cx, ws, B, tn, tm, true, dB, s));
             TSG_HIP(hipStreamSynchronize(s));
         }
     }
@@ -753,8 +803,7 @@ int tsg_tilespgemm(tsg_smatrix *A, tsg_smatrix *B, tsg_smatrix *C, unsigned int 
         int rc1 = TSG_OK;
         // (the step times' markers only with TSG_STAGE_EVENTS=1: each cost a few
         // us of GPU time on a ~1 ms call; the steps report 0 without them)
-        const char *sev = getenv("TSG_STAGE_EVENTS");
-        const bool se = sev && sev[0] == '1';
+        const bool se = cx.stage_ev;
         auto step1 = [&] {
             long long tp = 0;
             rc1 = hipSetDevice(cx.device) == hipSuccess ? TSG_OK : TSG_ERR_HIP;
@@ -793,8 +842,8 @@ int tsg_tilespgemm(tsg_smatrix *A, tsg_smatrix *B, tsg_smatrix *C, unsigned int 
             use_csr = false;
             evi[0] = 0, evi[1] = 1, evi[2] = 2, evi[3] = 3;
             t_s1 = -1.0;
-            rc = upload_tiles(cx, A, tm, tn, false, dA, s);
-            if (rc == TSG_OK) rc = upload_tiles(cx, B, tn, tm, true, dB, s);
+            rc = upload_tiles(cx, ws, A, tm, tn, false, dA, s);
+            if (rc == TSG_OK) rc = upload_tiles(cx, ws, B, tn, tm, true, dB, s);
             dC = tsg_dev_tiles{};
             if (rc == TSG_OK) rc = dev_tilespgemm(cx, dA, dB, dC, &st, s, cx.ev, nullptr, nullptr, nullptr, false);
         }
@@ -818,7 +867,6 @@ int tsg_tilespgemm(tsg_smatrix *A, tsg_smatrix *B, tsg_smatrix *C, unsigned int 
         C->m = dC.m; C->n = dC.n; C->nnz = dC.nnz;
         rc = download_tiles(dC, C, false, s);
     }
-    cx.pool.release_all_live();
     if (rc != TSG_OK) return rc;
     // the reference's steps at every tile size: step 1 | step 2 + scan | step 3
     // (the CSR route: step 1 overlaps step 2, its own stream's duration)
@@ -855,9 +903,10 @@ int tsg_tile2csr(tsg_smatrix *C, int tm, int tn) {
     TSG_TRY(lease.acquire());
     Context &cx = lease.cx();
     hipStream_t s = lease.stream();
+    PoolScope ws(cx);  // (the uploads; what the dev_* calls keep returns with the lease)
     tsg_dev_tiles t;
     tsg_dev_csr d;
-    TSG_TRY(upload_tiles(cx, C, tm, tm, false, t, s));
+    TSG_TRY(upload_tiles(cx, ws, C, tm, tm, false, t, s));
     int rc = dev_tile2csr(cx, t, d, s);
     if (rc == TSG_OK) {
         free(C->rowpointer); free(C->columnindex); free(C->value);
@@ -867,7 +916,6 @@ int tsg_tile2csr(tsg_smatrix *C, int tm, int tn) {
         if (rc == TSG_OK && hipStreamSynchronize(s) != hipSuccess) rc = TSG_ERR_HIP;
         C->nnz = d.nnz;
     }
-    cx.pool.release_all_live();
     return rc;
 }
 
@@ -905,6 +953,19 @@ int tsg_context_reset(tsg_context *ctx) {
     return TSG_OK;
 }
 
+int tsg_context_pool_stats(tsg_context *ctx, tsg_pool_stats *out) {
+    if (!ctx || !out) return TSG_ERR_INVALID;
+    *out = ctx->cx.pool.stats();
+    return TSG_OK;
+}
+
+int tsg_context_fail_alloc(tsg_context *ctx, long long nth) {
+    if (!ctx) return TSG_ERR_INVALID;
+    const bool was_pending = ctx->cx.pool.fail_pending();
+    ctx->cx.pool.fail_alloc(nth);
+    return was_pending ? 1 : 0;
+}
+
 int tsg_dev_malloc(tsg_context *ctx, void **ptr, size_t bytes) {
     if (!ctx || !ptr) return TSG_ERR_INVALID;
     return ctx->cx.pool.alloc(ptr, bytes);
@@ -940,40 +1001,31 @@ int tsg_memcpy_d2d(tsg_context *ctx, void *dst, const void *src, size_t bytes, v
 int tsg_dev_csr2tile_row_major(tsg_context *ctx, const tsg_dev_csr *A, int tm, int tn, void *stream,
                                tsg_dev_tiles *out) {
     if (!ctx || !A || !out || !valid_tiles(tm, tn)) return TSG_ERR_INVALID;
-    return dev_csr2tile_row_major(ctx->cx, *A, tm, tn, *out, (hipStream_t)stream);
+    return dev_result(dev_csr2tile_row_major(ctx->cx, *A, tm, tn, *out, (hipStream_t)stream), stream, out);
 }
 
 int tsg_dev_csr2tile_col_major(tsg_context *ctx, const tsg_dev_csr *B, int tm, int tn, void *stream,
                                tsg_dev_tiles *out) {
     if (!ctx || !B || !out || !valid_tiles(tm, tn)) return TSG_ERR_INVALID;
-    return dev_csr2tile_col_major(ctx->cx, *B, tm, tn, *out, (hipStream_t)stream);
+    return dev_result(dev_csr2tile_col_major(ctx->cx, *B, tm, tn, *out, (hipStream_t)stream), stream, out);
 }
 
 int tsg_dev_tilespgemm(tsg_context *ctx, const tsg_dev_tiles *A, const tsg_dev_tiles *B, void *stream,
                        tsg_dev_tiles *C, tsg_stats *stats) {
     if (!ctx || !A || !B || !C) return TSG_ERR_INVALID;
     if (!B->tile_rm2csc || !B->rm_mask || !B->rm_rowstart) return TSG_ERR_INVALID;
-    return dev_tilespgemm(ctx->cx, *A, *B, *C, stats, (hipStream_t)stream, nullptr, nullptr);
+    return dev_result(dev_tilespgemm(ctx->cx, *A, *B, *C, stats, (hipStream_t)stream, nullptr, nullptr), stream, C);
 }
 
 int tsg_dev_tile2csr(tsg_context *ctx, const tsg_dev_tiles *C, void *stream, tsg_dev_csr *out) {
     if (!ctx || !C || !out) return TSG_ERR_INVALID;
-    return dev_tile2csr(ctx->cx, *C, *out, (hipStream_t)stream);
+    return dev_result(dev_tile2csr(ctx->cx, *C, *out, (hipStream_t)stream), stream, out);
 }
 
 int tsg_dev_transpose(tsg_context *ctx, const tsg_dev_csr *A, void *stream, tsg_dev_csr *out) {
     if (!ctx || !A || !out) return TSG_ERR_INVALID;
-    return dev_transpose(ctx->cx, *A, *out, (hipStream_t)stream);
+    return dev_result(dev_transpose(ctx->cx, *A, *out, (hipStream_t)stream), stream, out);
 }
-
-static void release_tiles(Context &cx, tsg_dev_tiles &t) {
-    void *ps[] = {t.tile_ptr, t.tile_columnidx, t.tile_rowidx, t.tile_nnz, t.tile_csr_Ptr,
-                  t.tile_csr_Col, t.tile_csr_Value, t.mask, t.csc_tile_ptr, t.csc_tile_rowidx,
-                  t.tile_rm2csc, t.rm_mask, t.rm_rowstart};
-    for (void *p : ps) cx.put(p);
-    t = tsg_dev_tiles{};
-}
-
 
 // CSR in -> CSR out through the 16x16 tiled pipeline (C does not depend on the
 // tile size; other sizes are a layout choice of the host tile API).
@@ -983,13 +1035,9 @@ static int dev_spgemm16(Context &cx, const tsg_dev_csr *A, const tsg_dev_csr *B,
     tsg_stats st{};
     tsg_dev_tiles tA, tB, tC;
     auto h0 = std::chrono::steady_clock::now();
-    // the stage events (ev 8, 9, 0, 1, 3) only on request: each marker on the
-    // stream cost ~2-3 us of GPU time (cant 0.707 -> 0.692 ms without them, r5e1);
-    // the kernel bracket (ev 4, 5) and the end (ev 10) always
-    {
-        const char *se = getenv("TSG_STAGE_EVENTS");
-        cx.stage_ev = se && se[0] == '1';
-    }
+    // the stage events (ev 8, 9, 0, 1, 3) only on request (cx.stage_ev): each
+    // marker on the stream cost ~2-3 us of GPU time (cant 0.707 -> 0.692 ms
+    // without them, r5e1); the kernel bracket (ev 4, 5) and the end (ev 10) always
     // (no stats asked for -- the tiled route's product, a caller passing NULL:
     // not even the numeric phase's bracket on the row-merge and banded paths)
     hipEvent_t *const evp = stats || cx.stage_ev ? cx.ev : nullptr;
@@ -1003,6 +1051,10 @@ static int dev_spgemm16(Context &cx, const tsg_dev_csr *A, const tsg_dev_csr *B,
     // discarded: the full csr2tile below rebuilds A's tiles.)
     // (its last step -- the shares' sum into the flag -- rides on the row-merge
     // setup's binning kernel, or runs before the first read-back of another route)
+    // The scope owns what passes between the stages here -- the shares, the band
+    // windows, the row-merge plan, the tilings -- until each is put back or, for
+    // C's arrays, kept for the caller on success.
+    PoolScope ws(cx);
     SortedShares shares;
     // (A referencing at most 1/64 of B's rows -- the mawi prefix: 6,828 entries
     // against 226 M rows -- only the B rows A references are checked, 0.88 ->
@@ -1017,6 +1069,7 @@ static int dev_spgemm16(Context &cx, const tsg_dev_csr *A, const tsg_dev_csr *B,
         TSG_TRY(dev_rows_sorted_shares_ref(cx, *A, *B, cx.pinned + 1, &shares, s));
     else
         TSG_TRY(dev_rows_sorted_shares(cx, *B, cx.pinned + 1, &shares, s));
+    adopt_blocks(ws, shares);
     // Routing, B's rows column-sorted:
     //  * banded path (tsg_band.hip) when A averages >= 8 entries per row and every
     //    C row's reachable columns fit one window of <= 2,048 columns holding at
@@ -1030,9 +1083,9 @@ static int dev_spgemm16(Context &cx, const tsg_dev_csr *A, const tsg_dev_csr *B,
     //  * the staged tile pipeline below for the rest and for unsorted B rows
     //    (or rows repeating a column).
     // TSG_PATH=band / rows / tiles forces a path (band when its check passes).
-    const char *path = getenv("TSG_PATH");
-    const bool force_tiles = path && !strcmp(path, "tiles");
-    const bool force_band = path && !strcmp(path, "band"), force_rows = path && !strcmp(path, "rows");
+    const int force = cx.knobs.force_path;
+    const bool force_tiles = force == TSG_PATH_TILES, force_band = force == TSG_PATH_BAND,
+               force_rows = force == TSG_PATH_ROWS;
     if (!force_tiles) {
         bool band = false;
         BandWin bw;
@@ -1040,21 +1093,19 @@ static int dev_spgemm16(Context &cx, const tsg_dev_csr *A, const tsg_dev_csr *B,
         // check's read-back also brings the sortedness flag
         if (!force_rows && (force_band || (A->m > 0 && A->nnz >= 8LL * A->m))) {
             TSG_TRY(dev_band_check(cx, *A, *B, force_band, &band, &bw, s, &shares));  // (sums the shares too)
+            put_blocks(ws, shares);  // (stream-ordered reuse)
+            adopt_blocks(ws, bw);
         }
         if (band && cx.pinned[1] != 0) {  // unsorted B rows: the windows mean nothing
-            cx.put(bw.win);
-            cx.put(bw.width);
-            cx.put(bw.ebnd);
+            put_blocks(ws, bw);
             band = false;
         }
         long long path_id = -1;
         if (cx.stage_ev) TSG_HIP(hipEventRecord(cx.ev[9], s));
         if (band) {
-            const int rc = dev_spgemm_band(cx, *A, *B, bw, *C, &st, s, evp);
-            cx.put(bw.win);
-            cx.put(bw.width);
-            cx.put(bw.ebnd);
-            TSG_TRY(rc);
+            TSG_TRY(dev_spgemm_band(cx, *A, *B, bw, *C, &st, s, evp));
+            adopt_blocks(ws, *C);
+            put_blocks(ws, bw);
             path_id = TSG_PATH_BAND;
         } else {
             // the row-merge setup and the sortedness flag: one host round trip
@@ -1062,19 +1113,24 @@ static int dev_spgemm16(Context &cx, const tsg_dev_csr *A, const tsg_dev_csr *B,
             if (cx.stage_ev) TSG_HIP(hipEventRecord(cx.ev[0], s));
             RowsPlan plan;
             TSG_TRY(dev_rows_setup_async(cx, *A, *B, plan, s, shares.part ? &shares : nullptr));
+            put_blocks(ws, shares);  // (stream-ordered reuse)
+            adopt_blocks(ws, plan);
             TSG_TRY(stream_wait(s));
             dev_rows_setup_read(cx, plan);
             const bool bsorted0 = cx.pinned[1] == 0;
             if (bsorted0 && !force_band && (force_rows || dev_rows_accept(plan))) {
                 TSG_TRY(dev_rows_run(cx, *A, *B, plan, *C, &st, s, evp));
+                plan.rowpointer = nullptr;  // (now C's, and the scope's still)
+                ws.adopt(C->columnindex);
+                ws.adopt(C->value);
                 path_id = TSG_PATH_ROWS;
-            } else {
-                dev_rows_release(cx, plan);
             }
+            put_blocks(ws, plan);
         }
         if (path_id >= 0) {
             if (!evp) {  // (C complete on return, no marker)
                 TSG_TRY(stream_wait(s));
+                keep_blocks(ws, *C);
                 return TSG_OK;
             }
             // (the path returned with its stream drained; the end marker only for
@@ -1097,20 +1153,22 @@ static int dev_spgemm16(Context &cx, const tsg_dev_csr *A, const tsg_dev_csr *B,
             st.t_e2e_ms = std::chrono::duration<double, std::milli>(h1 - h0).count();
             st.t_malloc_ms = se ? st.t_e2e_ms - ev_ms(cx.ev[8], cx.ev[10]) : 0.0;
             if (st.t_malloc_ms < 0) st.t_malloc_ms = 0;
+            keep_blocks(ws, *C);
             if (stats) *stats = st;
             return TSG_OK;
         }
     }
     TSG_TRY(dev_rows_sorted_finish(cx, shares, s));  // (forced tiles: the flag is still owed)
+    put_blocks(ws, shares);                          // (stream-ordered reuse)
     if (ref_check) {  // (the referenced rows' flag: the tile pipeline needs all of B's)
         bool all_sorted = false;
         TSG_TRY(dev_rows_sorted(cx, *B, &all_sorted, s));
     }
     if (!cx.stage_ev) TSG_HIP(hipEventRecord(cx.ev[8], s));  // (the staged pipeline: its stage times always)
-    const char *md = getenv("TSG_STEP2_MODE");
-    const int forced = !md ? -1 : !strcmp(md, "elem") ? 1 : !strcmp(md, "tile") ? 0 : -1;
+    const int forced = cx.knobs.step2_mode;
     const double skip = forced == 1 ? 1e300 : forced == 0 ? 0.0 : kStep2ElemMaxTileDensity;
     TSG_TRY(dev_tile_structure(cx, *A, tm, tn, tA, s, skip));  // synchronises the stream
+    adopt_blocks(ws, tA);
     const bool bsorted = cx.pinned[1] == 0;
     const bool alias = A->rowpointer == B->rowpointer && A->columnindex == B->columnindex && A->m == B->m &&
                        A->n == B->n && tm == tn;
@@ -1138,22 +1196,32 @@ static int dev_spgemm16(Context &cx, const tsg_dev_csr *A, const tsg_dev_csr *B,
                 tB.numtile = -1;
             } else {
                 TSG_TRY(rc);
+                adopt_blocks(ws, tB);
             }
         }
         if (!s2elem) {
             TSG_TRY(dev_tile_masks(cx, *A, tA, &tA.mask, s));
-            if (b_is_a) tB.rm_mask = tA.mask;
-            else TSG_TRY(dev_tile_masks(cx, *B, tB, &tB.rm_mask, s));
+            ws.adopt(tA.mask);
+            if (b_is_a) {
+                tB.rm_mask = tA.mask;
+            } else {
+                TSG_TRY(dev_tile_masks(cx, *B, tB, &tB.rm_mask, s));
+                ws.adopt(tB.rm_mask);
+            }
         }
     } else {  // unsorted B rows: full csr2tile, tile-payload steps 2 and 3
-        release_tiles(cx, tA);
+        put_blocks(ws, tA);
         TSG_TRY(dev_csr2tile_row_major(cx, *A, tm, tn, tA, s));
+        adopt_blocks(ws, tA);
         TSG_TRY(dev_csr2tile_col_major(cx, *B, tm, tn, tB, s));
+        adopt_blocks(ws, tB);
     }
     TSG_HIP(hipEventRecord(cx.ev[9], s));
     // tile2csr is fused into step 3's epilogue on this path (C tiles stay materialised)
     TSG_TRY(dev_tilespgemm(cx, tA, tB, tC, &st, s, cx.ev, C, bsorted ? A : nullptr, bsorted ? B : nullptr,
                            s2elem));
+    adopt_blocks(ws, tC);  // (internal on this path: C is the CSR)
+    adopt_blocks(ws, *C);
     TSG_HIP(hipEventRecord(cx.ev[10], s));
     TSG_HIP(hipEventSynchronize(cx.ev[10]));
     auto h1 = std::chrono::steady_clock::now();
@@ -1169,34 +1237,34 @@ static int dev_spgemm16(Context &cx, const tsg_dev_csr *A, const tsg_dev_csr *B,
     st.t_e2e_ms = std::chrono::duration<double, std::milli>(h1 - h0).count();
     st.t_malloc_ms = st.t_e2e_ms - ev_ms(cx.ev[8], cx.ev[10]);
     if (st.t_malloc_ms < 0) st.t_malloc_ms = 0;
-    release_tiles(cx, tA);
-    if (b_is_a) tB = tsg_dev_tiles{};
-    release_tiles(cx, tB);
-    release_tiles(cx, tC);
+    keep_blocks(ws, *C);
     if (stats) *stats = st;
-    return TSG_OK;
+    return TSG_OK;  // (the tilings return to the pool here)
 }
 
 int tsg_dev_spgemm(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B, int tm, int tn,
                    void *stream, tsg_dev_csr *C, tsg_stats *stats) {
     if (!ctx || !A || !B || !C || !valid_tiles(tm, tn) || A->n != B->m) return TSG_ERR_INVALID;
     if (!tile_side_supported(tm) || !tile_side_supported(tn)) return TSG_ERR_UNSUPPORTED;
-    return dev_spgemm16(ctx->cx, A, B, (hipStream_t)stream, C, stats);
+    read_knobs(ctx->cx);
+    return dev_result(dev_spgemm16(ctx->cx, A, B, (hipStream_t)stream, C, stats), stream, C);
 }
 
 int tsg_dev_spgemm_sorted_b(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B, int b_checked_sorted,
                             int tm, int tn, void *stream, tsg_dev_csr *C, tsg_stats *stats) {
     if (!ctx || !A || !B || !C || !valid_tiles(tm, tn) || A->n != B->m) return TSG_ERR_INVALID;
     if (!tile_side_supported(tm) || !tile_side_supported(tn)) return TSG_ERR_UNSUPPORTED;
-    return dev_spgemm16(ctx->cx, A, B, (hipStream_t)stream, C, stats, b_checked_sorted == 1 ? 1 : -1);
+    read_knobs(ctx->cx);
+    return dev_result(dev_spgemm16(ctx->cx, A, B, (hipStream_t)stream, C, stats, b_checked_sorted == 1 ? 1 : -1),
+                      stream, C);
 }
 
 int tsg_dev_csr_rows_sorted(tsg_context *ctx, const tsg_dev_csr *M, void *stream, int *sorted) {
     if (!ctx || !M || !sorted || M->m < 0 || M->nnz < 0) return TSG_ERR_INVALID;
     bool ok = false;
-    TSG_TRY(dev_rows_sorted(ctx->cx, *M, &ok, (hipStream_t)stream));
-    *sorted = ok ? 1 : 0;
-    return TSG_OK;
+    const int rc = dev_result(dev_rows_sorted(ctx->cx, *M, &ok, (hipStream_t)stream), stream, sorted);
+    if (rc == TSG_OK) *sorted = ok ? 1 : 0;
+    return rc;
 }
 
 int tsg_spgemm_csr(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, int tm, int tn,
@@ -1207,9 +1275,10 @@ int tsg_spgemm_csr(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, i
     TSG_TRY(lease.acquire());
     Context &cx = lease.cx();
     hipStream_t s = lease.stream();
+    PoolScope ws(cx);  // (the uploads; what the dev_* calls keep returns with the lease)
     tsg_dev_csr dA, dB, dC;
-    TSG_TRY(upload_csr(cx, A, dA, s));
-    TSG_TRY(upload_csr(cx, B, dB, s));
+    TSG_TRY(upload_csr(ws, A, dA, s));
+    TSG_TRY(upload_csr(ws, B, dB, s));
     TSG_HIP(hipStreamSynchronize(s));
     int rc = tsg_dev_spgemm(lease.ctx(), &dA, &dB, tm, tn, s, &dC, stats);
     if (rc == TSG_OK) {
@@ -1220,7 +1289,6 @@ int tsg_spgemm_csr(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, i
         if (rc == TSG_OK) rc = download(&C->value, dC.value, (size_t)dC.nnz, s);
         if (rc == TSG_OK && hipStreamSynchronize(s) != hipSuccess) rc = TSG_ERR_HIP;
     }
-    cx.pool.release_all_live();
     return rc;
 }
 
@@ -1234,7 +1302,7 @@ int tsg_dev_numeric_plan_create(tsg_context *ctx, const tsg_dev_csr *A, const ts
     const int rc = dev_numeric_plan_create(ctx->cx, *A, *B, *Cpattern, pl->p, (hipStream_t)stream);
     if (rc != TSG_OK) {
         delete pl;
-        return rc;
+        return dev_result(rc, stream, plan);
     }
     ctx->plans.push_back(pl);
     if (info) *info = pl->p.info;
@@ -1287,15 +1355,16 @@ int tsg_spgemm_csr_numeric(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatr
     TSG_TRY(lease.acquire());
     Context &cx = lease.cx();
     hipStream_t s = lease.stream();
+    PoolScope ws(cx);  // (the uploads; what the dev_* calls keep returns with the lease)
     tsg_dev_csr dA, dB, dC;
-    int rc = upload_csr(cx, A, dA, s);
-    if (rc == TSG_OK) rc = upload_csr(cx, B, dB, s);
+    int rc = upload_csr(ws, A, dA, s);
+    if (rc == TSG_OK) rc = upload_csr(ws, B, dB, s);
     if (rc == TSG_OK) {
         dC.m = C->m; dC.n = C->n; dC.nnz = C->nnz;
-        rc = upload(cx, &dC.rowpointer, C->rowpointer, (size_t)C->m + 1, s);
+        rc = upload(ws, &dC.rowpointer, C->rowpointer, (size_t)C->m + 1, s);
     }
-    if (rc == TSG_OK) rc = upload(cx, &dC.columnindex, C->columnindex, (size_t)C->nnz, s);
-    if (rc == TSG_OK) rc = cx.get(&dC.value, (size_t)C->nnz + 1);
+    if (rc == TSG_OK) rc = upload(ws, &dC.columnindex, C->columnindex, (size_t)C->nnz, s);
+    if (rc == TSG_OK) rc = ws.get(&dC.value, (size_t)C->nnz + 1);
     if (rc == TSG_OK && hipStreamSynchronize(s) != hipSuccess) rc = TSG_ERR_HIP;
     tsg_numeric_plan *plan = nullptr;
     if (rc == TSG_OK) rc = tsg_dev_numeric_plan_create(lease.ctx(), &dA, &dB, &dC, s, &plan, nullptr);
@@ -1309,7 +1378,6 @@ int tsg_spgemm_csr_numeric(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatr
         }
         (void)tsg_dev_numeric_plan_destroy(lease.ctx(), plan);
     }
-    cx.pool.release_all_live();
     return rc;
 }
 

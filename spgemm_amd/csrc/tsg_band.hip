@@ -343,20 +343,21 @@ __global__ __launch_bounds__(WG) void k_band_compact(int m, const long long *sof
 
 // routing: whether every C row's window fits BD_SPAN and the windows are dense
 // (at least as many element products as window columns in all; `force` drops
-// the density test).  Leaves the windows in *win_out (caller-owned, cx.put)
-// when the answer is yes.
+// the density test).  Leaves the windows in *bw (the caller's scope adopts
+// them) when the answer is yes.
 int dev_band_check(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, bool force, bool *ok, BandWin *bw,
                    hipStream_t s, SortedShares *sh) {
     *ok = false;
     *bw = BandWin{};
     if (A.m <= 0 || A.n != B.m) return sh ? dev_rows_sorted_finish(cx, *sh, s) : TSG_OK;
+    PoolScope ws(cx);
     int2 *win = nullptr, *ebnd = nullptr;
     long long *width = nullptr;
     int *bad = nullptr;
-    TSG_TRY(cx.get(&win, (size_t)A.m));
-    TSG_TRY(cx.get(&width, (size_t)A.m + 1));
-    TSG_TRY(cx.get(&ebnd, (size_t)A.nnz + 1));
-    TSG_TRY(cx.get(&bad, 6 * BD_SLOTS));
+    TSG_TRY(ws.get(&win, (size_t)A.m));
+    TSG_TRY(ws.get(&width, (size_t)A.m + 1));
+    TSG_TRY(ws.get(&ebnd, (size_t)A.nnz + 1));
+    TSG_TRY(ws.get(&bad, 6 * BD_SLOTS));
     TSG_HIP(hipMemsetAsync(bad, 0, 6 * BD_SLOTS * sizeof(int), s));
     k_band_stats<<<grid_for(A.m, WG / 16, 16384), WG, 0, s>>>(A.rowpointer, A.columnindex, A.m, B.rowpointer,
                                                         B.columnindex, win, width, bad, ebnd);
@@ -364,22 +365,13 @@ int dev_band_check(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, bool
     k_band_stats_final<<<1, WG, 0, s>>>(bad, shares ? sh->part : nullptr, shares ? sh->nb : 0,
                                          shares ? sh->dflag : nullptr);
     TSG_HIP(hipGetLastError());
-    if (sh) {
-        cx.put(sh->part);  // (stream-ordered reuse)
-        *sh = SortedShares{};
-    }
     TSG_HIP(hipMemcpyAsync(cx.pinned + 8, bad, 6 * sizeof(int), hipMemcpyDeviceToHost, s));
     TSG_TRY(stream_wait(s));
-    cx.put(bad);
     const long long products = *reinterpret_cast<const long long *>(cx.pinned + 10);
     const long long wcols = *reinterpret_cast<const long long *>(cx.pinned + 12);
     if (cx.pinned[8] == 0 && (force || products >= wcols)) {
         *ok = true;
-        *bw = BandWin{win, width, products, wcols, ebnd};
-    } else {
-        cx.put(win);
-        cx.put(width);
-        cx.put(ebnd);
+        *bw = BandWin{ws.keep(win), ws.keep(width), products, wcols, ws.keep(ebnd)};
     }
     return TSG_OK;
 }
@@ -391,22 +383,22 @@ __global__ __launch_bounds__(WG) void k_band_ebnd(const int *ciA, long nnzA, con
     }
 }
 
-// CSR in -> CSR out for a banded product (windows from dev_band_check; their
-// width array becomes the staging offsets).
+// CSR in -> CSR out for a banded product (windows from dev_band_check, the
+// caller's; their width array becomes the staging offsets).
 // ev (optional): 0 start | 1 set up | 4..5 the row kernel | 3 end
-int dev_spgemm_band(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, BandWin &bw, tsg_dev_csr &C,
+int dev_spgemm_band(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const BandWin &bw, tsg_dev_csr &C,
                     tsg_stats *st, hipStream_t s, hipEvent_t *ev) {
     const int m = A.m;
     C = tsg_dev_csr{};
     C.m = m;
     C.n = B.n;
     if (ev) TSG_HIP(hipEventRecord(ev[0], s));
+    PoolScope ws(cx);
     int2 *ebnd = bw.ebnd;  // (filled by the window check's statistics kernel)
-    bw.ebnd = nullptr;
     int *Scol = nullptr;
     double *Sval = nullptr;
     if (!ebnd) {
-        TSG_TRY(cx.get(&ebnd, (size_t)A.nnz + 1));
+        TSG_TRY(ws.get(&ebnd, (size_t)A.nnz + 1));
         if (A.nnz > 0) k_band_ebnd<<<grid_for(A.nnz, WG, 16384), WG, 0, s>>>(A.columnindex, A.nnz, B.rowpointer, ebnd);
         TSG_HIP(hipGetLastError());
     }
@@ -415,9 +407,9 @@ int dev_spgemm_band(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, Ban
     // 1.9x), else the widths' prefix (narrow windows: no near-2 GiB staging)
     const bool fixed = (long long)m * BD_SPAN * 12 <= (2LL << 30) && (long long)m * BD_SPAN <= 4 * bw.wcols;
     const long long slots = fixed ? (long long)m * BD_SPAN : bw.wcols;
-    TSG_TRY(cx.get(&Scol, (size_t)slots + 1));
-    TSG_TRY(cx.get(&Sval, (size_t)slots + 1));
-    TSG_TRY(cx.get(&C.rowpointer, (size_t)m + 1));
+    TSG_TRY(ws.get(&Scol, (size_t)slots + 1));
+    TSG_TRY(ws.get(&Sval, (size_t)slots + 1));
+    TSG_TRY(ws.get(&C.rowpointer, (size_t)m + 1));
     if (!fixed) {  // window widths -> staging offsets
         const int rc = dev_scan_i64_fused(cx, bw.width, (long)m + 1, s);
         if (rc == TSG_ERR_UNSUPPORTED) TSG_TRY(scan_exclusive_i64(cx, bw.width, (long)m + 1, s));
@@ -446,20 +438,20 @@ int dev_spgemm_band(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, Ban
         if (rc == TSG_ERR_UNSUPPORTED) fused = false;
         else TSG_TRY(rc);
     }
-    if (fused && (cx.get(&C.columnindex, (size_t)bw.wcols + 1) != TSG_OK ||
-                  cx.get(&C.value, (size_t)bw.wcols + 1) != TSG_OK)) {
+    if (fused && (ws.get(&C.columnindex, (size_t)bw.wcols + 1) != TSG_OK ||
+                  ws.get(&C.value, (size_t)bw.wcols + 1) != TSG_OK)) {
         (void)hipGetLastError();
-        cx.put(C.columnindex);
+        ws.put(C.columnindex);
         C.columnindex = nullptr;
         TSG_TRY(stream_wait(s));  // (the fused scan's nnz(C), then C sized exactly)
         nnz = *hnnz;
-        TSG_TRY(cx.get(&C.columnindex, (size_t)nnz + 1));
-        TSG_TRY(cx.get(&C.value, (size_t)nnz + 1));
+        TSG_TRY(ws.get(&C.columnindex, (size_t)nnz + 1));
+        TSG_TRY(ws.get(&C.value, (size_t)nnz + 1));
     } else if (!fused) {
         TSG_TRY(scan_exclusive_i32_total(cx, C.rowpointer, (long)m + 1, s, &nnz));
         if (nnz > 0x7fffffffLL) return TSG_ERR_OVERFLOW;
-        TSG_TRY(cx.get(&C.columnindex, (size_t)nnz + 1));
-        TSG_TRY(cx.get(&C.value, (size_t)nnz + 1));
+        TSG_TRY(ws.get(&C.columnindex, (size_t)nnz + 1));
+        TSG_TRY(ws.get(&C.value, (size_t)nnz + 1));
     }
     if (m > 0)
         k_band_compact<<<grid_for(m, WAVES, 16384), WG, 0, s>>>(m, soff, C.rowpointer, Scol, Sval, C.columnindex,
@@ -470,9 +462,7 @@ int dev_spgemm_band(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, Ban
     if (fused) nnz = *hnnz;
     if (nnz > 0x7fffffffLL) return TSG_ERR_OVERFLOW;
     C.nnz = (int)nnz;
-    cx.put(ebnd);
-    cx.put(Scol);
-    cx.put(Sval);
+    keep_blocks(ws, C);
     if (st) {
         st->nnzC = C.nnz;
         st->tile_products = bw.products;

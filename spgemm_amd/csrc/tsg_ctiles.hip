@@ -252,19 +252,20 @@ namespace tsg {
 int dev_ctiles_from_csr(Context &cx, const tsg_dev_csr &Cc, tsg_dev_tiles &C, hipStream_t s) {
     if (C.tile_m != 16 || C.tile_n != 16 || Cc.m != C.m) return TSG_ERR_INVALID;
     const size_t nt1 = (size_t)C.numtile + 1;
-    TSG_TRY(cx.get(&C.tile_nnz, nt1));
-    TSG_TRY(cx.get(&C.tile_csr_Ptr, nt1 * 16));
-    TSG_TRY(cx.get(&C.mask, nt1 * 16));
-    TSG_TRY(cx.get(&C.tile_csr_Col, (size_t)Cc.nnz + 1));
-    TSG_TRY(cx.get(&C.tile_csr_Value, (size_t)Cc.nnz + 1));
+    PoolScope ws(cx);
+    TSG_TRY(ws.get(&C.tile_nnz, nt1));
+    TSG_TRY(ws.get(&C.tile_csr_Ptr, nt1 * 16));
+    TSG_TRY(ws.get(&C.mask, nt1 * 16));
+    TSG_TRY(ws.get(&C.tile_csr_Col, (size_t)Cc.nnz + 1));
+    TSG_TRY(ws.get(&C.tile_csr_Value, (size_t)Cc.nnz + 1));
     C.nnz = Cc.nnz;
     int *fail = nullptr, *ubase = nullptr, *ulo = nullptr;
     int4 *units = nullptr;
     const long umax = (long)C.numtile / CT_TC + C.tilem + 1;  // (units: an upper bound)
-    TSG_TRY(cx.get(&fail, 2));
-    TSG_TRY(cx.get(&ubase, (size_t)C.tilem + 1));
-    TSG_TRY(cx.get(&units, (size_t)umax));
-    TSG_TRY(cx.get(&ulo, 16 * (size_t)umax + 16));
+    TSG_TRY(ws.get(&fail, 2));
+    TSG_TRY(ws.get(&ubase, (size_t)C.tilem + 1));
+    TSG_TRY(ws.get(&units, (size_t)umax));
+    TSG_TRY(ws.get(&ulo, 16 * (size_t)umax + 16));
     TSG_HIP(hipMemsetAsync(fail, 0, 2 * sizeof(int), s));
     cx.pinned[9] = Cc.nnz;  // tile_nnz[numtile] = nnz(C)
     TSG_HIP(hipMemcpyAsync(C.tile_nnz + C.numtile, cx.pinned + 9, sizeof(int), hipMemcpyHostToDevice, s));
@@ -284,11 +285,8 @@ int dev_ctiles_from_csr(Context &cx, const tsg_dev_csr &Cc, tsg_dev_tiles &C, hi
     TSG_HIP(hipGetLastError());
     cx.pinned[8] = 0;
     TSG_HIP(hipMemcpyAsync(cx.pinned + 8, fail, sizeof(int), hipMemcpyDeviceToHost, s));
-    cx.put(fail);  // (stream-ordered reuse: the copies above precede any later use)
-    cx.put(ubase);
-    cx.put(units);
-    cx.put(ulo);
-    return TSG_OK;
+    keep_blocks(ws, C);
+    return TSG_OK;  // (the temporaries return here; stream-ordered reuse: the copies above precede any later use)
 }
 
 }  // namespace tsg

@@ -99,14 +99,14 @@ template <class T> static int scan_exclusive(Context &cx, T *a, long n, hipStrea
     // for mc2depi's 1.7 M entries, 25 vs 17 us for webbase's 3.1 M -- the
     // inclusive prefix crosses HBM once per 64 tiles of look-back, and the
     // status array needs its own memset)
+    PoolScope ws(cx);
     T *part = nullptr;
-    TSG_TRY(cx.get(&part, nb));
+    TSG_TRY(ws.get(&part, nb));
     k_scan_reduce<T><<<(unsigned)nb, WG, 0, s>>>(a, n, part);
     TSG_HIP(hipGetLastError());
     TSG_TRY(scan_exclusive(cx, part, nb, s));
     k_scan_apply<T><<<(unsigned)nb, WG, 0, s>>>(a, n, part);
     TSG_HIP(hipGetLastError());
-    cx.put(part);
     return TSG_OK;
 }
 
@@ -138,11 +138,12 @@ template <class Fn>
 static int scan_i32_total_impl(Context &cx, int *a, long n, hipStream_t s, long long *total, Fn &&before_read,
                                const long long *extra_d, long long *extra_h) {
     *total = 0;
+    PoolScope ws(cx);
     long long *part = nullptr;
     long nb = 0;
     if (n > 0) {
         nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-        TSG_TRY(cx.get(&part, (size_t)nb + 1));
+        TSG_TRY(ws.get(&part, (size_t)nb + 1));
         k_scan_reduce_wide<<<(unsigned)nb, WG, 0, s>>>(a, n, part);
         TSG_HIP(hipGetLastError());
         TSG_TRY(scan_exclusive(cx, part, nb + 1, s));
@@ -155,7 +156,6 @@ static int scan_i32_total_impl(Context &cx, int *a, long n, hipStream_t s, long 
     if (part || extra_d) TSG_TRY(stream_wait(s));
     if (part) *total = cx.pinned64[0];
     if (extra_d) *extra_h = cx.pinned64[1];
-    cx.put(part);
     return *total > 0x7fffffffll ? TSG_ERR_OVERFLOW : TSG_OK;
 }
 int scan_exclusive_i32_total(Context &cx, int *a, long n, hipStream_t s, long long *total) {
@@ -339,11 +339,12 @@ __global__ __launch_bounds__(WG) void k_sort_t4_copy(u64 *keys, const u64 *tmp, 
 
 int segmented_sort_u64(Context &cx, u64 *keys, const int *seg, int nseg, long total, hipStream_t s) {
     if (nseg <= 0 || total <= 1) return TSG_OK;
+    PoolScope ws(cx);
     int *lists = nullptr, *counts = nullptr;
     u64 *tmp = nullptr;
-    TSG_TRY(cx.get(&lists, (size_t)4 * nseg));
-    TSG_TRY(cx.get(&counts, 4));
-    TSG_TRY(cx.get(&tmp, (size_t)total));
+    TSG_TRY(ws.get(&lists, (size_t)4 * nseg));
+    TSG_TRY(ws.get(&counts, 4));
+    TSG_TRY(ws.get(&tmp, (size_t)total));
     TSG_HIP(hipMemsetAsync(counts, 0, 4 * sizeof(int), s));
     k_sort_classify<<<grid_for(nseg, WG, 4096), WG, 0, s>>>(seg, nseg, lists, counts);
     k_sort_t1<<<grid_for(nseg, WG, 2048), WG, 0, s>>>(keys, seg, lists, counts);
@@ -354,9 +355,6 @@ int segmented_sort_u64(Context &cx, u64 *keys, const int *seg, int nseg, long to
     k_sort_t4_place<<<g4, WG, 0, s>>>(keys, tmp, seg, lists + 3L * nseg, counts + 3);
     k_sort_t4_copy<<<g4, WG, 0, s>>>(keys, tmp, seg, lists + 3L * nseg, counts + 3);
     TSG_HIP(hipGetLastError());
-    cx.put(lists);
-    cx.put(counts);
-    cx.put(tmp);
     return TSG_OK;
 }
 
@@ -439,13 +437,14 @@ int dev_transpose(Context &cx, const tsg_dev_csr &A, tsg_dev_csr &out, hipStream
     out.m = A.n;
     out.n = A.m;
     out.nnz = A.nnz;
-    TSG_TRY(cx.get(&out.rowpointer, (size_t)A.n + 1));
-    TSG_TRY(cx.get(&out.columnindex, (size_t)A.nnz + 1));
-    TSG_TRY(cx.get(&out.value, (size_t)A.nnz + 1));
+    PoolScope ws(cx);
+    TSG_TRY(ws.get(&out.rowpointer, (size_t)A.n + 1));
+    TSG_TRY(ws.get(&out.columnindex, (size_t)A.nnz + 1));
+    TSG_TRY(ws.get(&out.value, (size_t)A.nnz + 1));
     int *fill = nullptr;
     u64 *keys = nullptr;
-    TSG_TRY(cx.get(&fill, (size_t)A.n + 1));
-    TSG_TRY(cx.get(&keys, (size_t)A.nnz + 1));
+    TSG_TRY(ws.get(&fill, (size_t)A.n + 1));
+    TSG_TRY(ws.get(&keys, (size_t)A.nnz + 1));
     TSG_HIP(hipMemsetAsync(out.rowpointer, 0, ((size_t)A.n + 1) * sizeof(int), s));
     TSG_HIP(hipMemsetAsync(fill, 0, ((size_t)A.n + 1) * sizeof(int), s));
     if (A.nnz > 0)
@@ -459,8 +458,7 @@ int dev_transpose(Context &cx, const tsg_dev_csr &A, tsg_dev_csr &out, hipStream
         k_transpose_finish<<<grid_for(A.nnz, WG * 4, 8192), WG, 0, s>>>(keys, A.nnz, A.value,
                                                                         out.columnindex, out.value);
     TSG_HIP(hipGetLastError());
-    cx.put(fill);
-    cx.put(keys);
+    keep_blocks(ws, out);
     return TSG_OK;
 }
 
@@ -645,11 +643,12 @@ static int csr2tile_impl(Context &cx, const tsg_dev_csr &M, bool colmajor, tsg_d
     out.m = m; out.n = n; out.nnz = nnz;
     out.tile_m = TR; out.tile_n = TC;
     out.tilem = tilem; out.tilen = tilen;
+    PoolScope ws(cx);
     int *seg = nullptr, *U = nullptr;
     u64 *keys = nullptr;
-    TSG_TRY(cx.get(&seg, (size_t)tilem + 1));
-    TSG_TRY(cx.get(&keys, (size_t)nnz + 1));
-    TSG_TRY(cx.get(&out.tile_ptr, (size_t)tilem + 1));
+    TSG_TRY(ws.get(&seg, (size_t)tilem + 1));
+    TSG_TRY(ws.get(&keys, (size_t)nnz + 1));
+    TSG_TRY(ws.get(&out.tile_ptr, (size_t)tilem + 1));
     k_strided_starts<<<grid_for(tilem + 1, WG, 4096), WG, 0, s>>>(M.rowpointer, m, TR, tilem, seg);
     if (m > 0) {
         if (colmajor)
@@ -668,13 +667,13 @@ static int csr2tile_impl(Context &cx, const tsg_dev_csr &M, bool colmajor, tsg_d
     TSG_TRY(read_i32(cx, out.tile_ptr + tilem, &numtile, s));
     out.numtile = numtile;
     const size_t nt1 = (size_t)numtile + 1;
-    TSG_TRY(cx.get(&out.tile_columnidx, nt1));
-    TSG_TRY(cx.get(&out.tile_rowidx, nt1));
-    TSG_TRY(cx.get(&out.tile_nnz, nt1));
-    TSG_TRY(cx.get(&out.tile_csr_Ptr, nt1 * TR));
-    TSG_TRY(cx.get(&out.tile_csr_Col, (size_t)nnz + 1));
-    TSG_TRY(cx.get(&out.tile_csr_Value, (size_t)nnz + 1));
-    TSG_TRY(cx.get(&out.mask, nt1 * TR * (TC / 16)));
+    TSG_TRY(ws.get(&out.tile_columnidx, nt1));
+    TSG_TRY(ws.get(&out.tile_rowidx, nt1));
+    TSG_TRY(ws.get(&out.tile_nnz, nt1));
+    TSG_TRY(ws.get(&out.tile_csr_Ptr, nt1 * TR));
+    TSG_TRY(ws.get(&out.tile_csr_Col, (size_t)nnz + 1));
+    TSG_TRY(ws.get(&out.tile_csr_Value, (size_t)nnz + 1));
+    TSG_TRY(ws.get(&out.mask, nt1 * TR * (TC / 16)));
     const int gfill = grid_for(tilem, WAVES, 8192);
     if (!colmajor) {
         k_c2t_fill<TR, TC, FILL_A><<<gfill, WG, 0, s>>>(keys, seg, tilem, M.columnindex, M.value, out.tile_ptr,
@@ -686,14 +685,14 @@ static int csr2tile_impl(Context &cx, const tsg_dev_csr &M, bool colmajor, tsg_d
     } else {
         int *nnz_rm = nullptr, *fill = nullptr;
         u64 *tkeys = nullptr;
-        TSG_TRY(cx.get(&nnz_rm, nt1));
-        TSG_TRY(cx.get(&fill, (size_t)tilen + 1));
-        TSG_TRY(cx.get(&tkeys, nt1));
-        TSG_TRY(cx.get(&out.csc_tile_ptr, (size_t)tilen + 1));
-        TSG_TRY(cx.get(&out.csc_tile_rowidx, nt1));
-        TSG_TRY(cx.get(&out.tile_rm2csc, nt1));
-        TSG_TRY(cx.get(&out.rm_mask, nt1 * TR * (TC / 16)));
-        TSG_TRY(cx.get(&out.rm_rowstart, nt1 * (TR + 1)));
+        TSG_TRY(ws.get(&nnz_rm, nt1));
+        TSG_TRY(ws.get(&fill, (size_t)tilen + 1));
+        TSG_TRY(ws.get(&tkeys, nt1));
+        TSG_TRY(ws.get(&out.csc_tile_ptr, (size_t)tilen + 1));
+        TSG_TRY(ws.get(&out.csc_tile_rowidx, nt1));
+        TSG_TRY(ws.get(&out.tile_rm2csc, nt1));
+        TSG_TRY(ws.get(&out.rm_mask, nt1 * TR * (TC / 16)));
+        TSG_TRY(ws.get(&out.rm_rowstart, nt1 * (TR + 1)));
         k_c2t_fill<TR, TC, FILL_B_STRUCT><<<gfill, WG, 0, s>>>(keys, seg, tilem, M.columnindex, M.value,
                                                               out.tile_ptr, out.tile_columnidx, out.tile_rowidx,
                                                               nnz_rm, nullptr, nullptr, nullptr, nullptr,
@@ -719,12 +718,8 @@ static int csr2tile_impl(Context &cx, const tsg_dev_csr &M, bool colmajor, tsg_d
                                                                out.tile_csr_Value, out.mask, out.tile_rm2csc,
                                                                out.tile_nnz, out.rm_mask, out.rm_rowstart);
         TSG_HIP(hipGetLastError());
-        cx.put(nnz_rm);
-        cx.put(fill);
-        cx.put(tkeys);
     }
-    cx.put(seg);
-    cx.put(keys);
+    keep_blocks(ws, out);
     return TSG_OK;
 }
 
@@ -1244,12 +1239,14 @@ __global__ __launch_bounds__(WG) void k_tile_masks(const int *rowptr, const int 
 
 int dev_tile_masks(Context &cx, const tsg_dev_csr &M, tsg_dev_tiles &t, u16 **mask_out, hipStream_t s) {
     const size_t words = ((size_t)t.numtile * t.tile_m * (t.tile_n / 16) + 2) & ~(size_t)1;
-    TSG_TRY(cx.get(mask_out, words));
+    PoolScope ws(cx);
+    TSG_TRY(ws.get(mask_out, words));
     TSG_HIP(hipMemsetAsync(*mask_out, 0, words * sizeof(u16), s));
     if (M.m > 0)
         k_tile_masks<<<grid_for(M.m, WG, 16384), WG, 0, s>>>(M.rowpointer, M.columnindex, M.m, t.tile_m, t.tile_n,
                                                              t.tile_ptr, t.tile_columnidx, *mask_out);
     TSG_HIP(hipGetLastError());
+    ws.keep(*mask_out);
     return TSG_OK;
 }
 
@@ -1264,9 +1261,10 @@ int dev_tile_structure(Context &cx, const tsg_dev_csr &M, int tr, int tc, tsg_de
     window_for(out.tilen, &win, &nwin);
     if ((long)out.tilem * nwin >= (1L << 31) - 1) return TSG_ERR_UNSUPPORTED;
     const long nunits = (long)out.tilem * nwin;
+    PoolScope ws(cx);
     int *ucnt = nullptr;
-    TSG_TRY(cx.get(&ucnt, (size_t)nunits + 1));
-    TSG_TRY(cx.get(&out.tile_ptr, (size_t)out.tilem + 1));
+    TSG_TRY(ws.get(&ucnt, (size_t)nunits + 1));
+    TSG_TRY(ws.get(&out.tile_ptr, (size_t)out.tilem + 1));
     const int g = grid_for(nunits, 1, 16384);
     const bool wave16 = out.tilem > 0 && tr == 16 && tc == 16 && nwin == 1 && !(ablate_bits() & 2048);
     if (!wave16) TSG_HIP(hipMemsetAsync(ucnt + nunits, 0, sizeof(int), s));  // (k_tcount16 zeroes it)
@@ -1286,15 +1284,15 @@ int dev_tile_structure(Context &cx, const tsg_dev_csr &M, int tr, int tc, tsg_de
     k_rows_from_units<<<grid_for(out.tilem + 1, WG, 4096), WG, 0, s>>>(ucnt, out.tilem, nwin, out.tile_ptr);
     TSG_TRY(read_i32(cx, out.tile_ptr + out.tilem, &out.numtile, s));
     if ((double)M.nnz < skip_emit_density * (double)out.numtile) {  // caller needs the counts only
-        cx.put(ucnt);
+        keep_blocks(ws, out);
         return TSG_OK;
     }
-    TSG_TRY(cx.get(&out.tile_columnidx, (size_t)out.numtile + 1));
+    TSG_TRY(ws.get(&out.tile_columnidx, (size_t)out.numtile + 1));
     if (out.tilem > 0)
         k_tstruct<1><<<g, WG, 0, s>>>(M.rowpointer, M.columnindex, M.m, tr, tc, out.tilem, out.tilen, nwin, win,
                                       nullptr, ucnt, out.tile_columnidx);
     TSG_HIP(hipGetLastError());
-    cx.put(ucnt);
+    keep_blocks(ws, out);
     return TSG_OK;
 }
 
@@ -1407,15 +1405,17 @@ __global__ __launch_bounds__(SRT_FIN) void k_rows_sorted_final(const int *part, 
 int dev_rows_sorted_shares(Context &cx, const tsg_dev_csr &M, int *host_flag, SortedShares *sh, hipStream_t s) {
     *host_flag = 0;
     *sh = SortedShares{};
+    PoolScope ws(cx);
     if (M.m > 0 && M.nnz > 1) {
         TSG_HIP(hipHostGetDevicePointer((void **)&sh->dflag, host_flag, 0));
         const long n = std::max<long>(M.nnz, M.m);
         const long nb = std::min<long>((n + WG * SRT_PT - 1) / (WG * SRT_PT), SRT_MAXB);
-        TSG_TRY(cx.get(&sh->part, (size_t)nb));
+        TSG_TRY(ws.get(&sh->part, (size_t)nb));
         sh->nb = (int)nb;
         k_rows_sorted_count<<<(unsigned)nb, WG, 0, s>>>(M.rowpointer, M.columnindex, M.m, M.nnz, sh->part);
     }
     TSG_HIP(hipGetLastError());
+    ws.keep(sh->part);
     return TSG_OK;
 }
 // Sortedness of the B rows A references only (a row block of A against a far
@@ -1487,15 +1487,16 @@ int dev_rows_sorted_shares_ref(Context &cx, const tsg_dev_csr &A, const tsg_dev_
     *sh = SortedShares{};
     if (B.m <= 0 || B.nnz <= 1 || A.nnz <= 0) return TSG_OK;
     TSG_HIP(hipHostGetDevicePointer((void **)&sh->dflag, host_flag, 0));
+    PoolScope ws(cx);
     u32 *bits = nullptr;
     int2 *items = nullptr;
     int *shorts = nullptr, *longs = nullptr;
     const size_t nw = ((size_t)B.m + 31) / 32;
-    TSG_TRY(cx.get(&bits, nw + 3));  // (+3: the three queue counts after the bits)
-    TSG_TRY(cx.get(&items, (size_t)A.nnz));
-    TSG_TRY(cx.get(&shorts, (size_t)A.nnz));
-    TSG_TRY(cx.get(&longs, (size_t)A.nnz));
-    TSG_TRY(cx.get(&sh->part, (size_t)SRT_REFB));
+    TSG_TRY(ws.get(&bits, nw + 3));  // (+3: the three queue counts after the bits)
+    TSG_TRY(ws.get(&items, (size_t)A.nnz));
+    TSG_TRY(ws.get(&shorts, (size_t)A.nnz));
+    TSG_TRY(ws.get(&longs, (size_t)A.nnz));
+    TSG_TRY(ws.get(&sh->part, (size_t)SRT_REFB));
     int *const cnt = reinterpret_cast<int *>(bits + nw);
     TSG_HIP(hipMemsetAsync(bits, 0, (nw + 3) * sizeof(u32), s));
     k_ref_mark<<<grid_for(A.nnz, WG, 16384), WG, 0, s>>>(A.columnindex, A.nnz, B.rowpointer, bits, items, shorts,
@@ -1503,25 +1504,21 @@ int dev_rows_sorted_shares_ref(Context &cx, const tsg_dev_csr &A, const tsg_dev_
     k_ref_check<<<SRT_REFB, WG, 0, s>>>(B.rowpointer, B.columnindex, items, shorts, longs, cnt, sh->part);
     TSG_HIP(hipGetLastError());
     sh->nb = SRT_REFB;
-    cx.put(bits);  // (stream-ordered reuse)
-    cx.put(items);
-    cx.put(shorts);
-    cx.put(longs);
-    return TSG_OK;
+    ws.keep(sh->part);
+    return TSG_OK;  // (bits, items, shorts, longs return here: stream-ordered reuse)
 }
-int dev_rows_sorted_finish(Context &cx, SortedShares &sh, hipStream_t s) {
-    if (sh.part) {
-        k_rows_sorted_final<<<1, SRT_FIN, 0, s>>>(sh.part, sh.nb, sh.dflag);
-        cx.put(sh.part);  // (stream-ordered reuse)
-    }
-    sh = SortedShares{};
+// (queues the sum only: the shares stay their owner's, who puts them back after this)
+int dev_rows_sorted_finish(Context &, const SortedShares &sh, hipStream_t s) {
+    if (sh.part) k_rows_sorted_final<<<1, SRT_FIN, 0, s>>>(sh.part, sh.nb, sh.dflag);
     TSG_HIP(hipGetLastError());
     return TSG_OK;
 }
 int dev_rows_sorted_async(Context &cx, const tsg_dev_csr &M, int *host_flag, hipStream_t s) {
+    PoolScope ws(cx);
     SortedShares sh;
     TSG_TRY(dev_rows_sorted_shares(cx, M, host_flag, &sh, s));
-    return dev_rows_sorted_finish(cx, sh, s);
+    adopt_blocks(ws, sh);
+    return dev_rows_sorted_finish(cx, sh, s);  // (the shares return here: stream-ordered reuse)
 }
 int dev_rows_sorted(Context &cx, const tsg_dev_csr &M, bool *sorted, hipStream_t s) {
     TSG_TRY(dev_rows_sorted_async(cx, M, cx.pinned + 1, s));
@@ -2477,11 +2474,12 @@ int dev_step1(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, tsg_d
     window_for(tilenB, &win, &nwin);
     if ((long)tilemA * nwin >= (1L << 31) - 1) return TSG_ERR_UNSUPPORTED;
     const long nunits1 = (long)tilemA * nwin;
+    PoolScope ws(cx);
     int *ucnt = nullptr;
     u64 *prod = nullptr;
-    TSG_TRY(cx.get(&ucnt, (size_t)nunits1 + 1));
-    TSG_TRY(cx.get(&prod, 1));
-    TSG_TRY(cx.get(&C.tile_ptr, (size_t)tilemA + 1));
+    TSG_TRY(ws.get(&ucnt, (size_t)nunits1 + 1));
+    TSG_TRY(ws.get(&prod, 1));
+    TSG_TRY(ws.get(&C.tile_ptr, (size_t)tilemA + 1));
     const int g1 = grid_for(nunits1, 1, 16384);
     // k_step1_cap (element level) or k_step1_cap_tiles (tile level) runs, and zeroes these
     const bool capk = ((el && ebnd) || !el) && tilemA > 0 && !(ablate_bits() & 512);
@@ -2505,7 +2503,7 @@ int dev_step1(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, tsg_d
         fill_ebnd = false;
     }
     if (capk) {
-        TSG_TRY(cx.get(&ubuf_off, (size_t)nunits1 + 1));
+        TSG_TRY(ws.get(&ubuf_off, (size_t)nunits1 + 1));
         if (el)
             k_step1_cap<<<grid_for((long)tilemA * 64, WG, 8192), WG, 0, s>>>(
                 Ael->rowpointer, Ael->m, ebnd, tilemA, nwin, win, tilenB, ubuf_off,
@@ -2520,11 +2518,11 @@ int dev_step1(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, tsg_d
         const double est = el ? (double)Ael->nnz * ((double)Bel->nnz / (double)(Bel->m > 0 ? Bel->m : 1))
                               : (double)A.numtile * ((double)B.numtile / (double)(B.tilem > 0 ? B.tilem : 1));
         if ((double)slots <= 2.0 * est + (double)(1 << 26) && slots < (1LL << 31) &&
-            cx.get(&ubuf, (size_t)slots + 1) == TSG_OK) {
+            ws.get(&ubuf, (size_t)slots + 1) == TSG_OK) {
         } else {
             (void)hipGetLastError();
             ubuf = nullptr;
-            cx.put(ubuf_off);
+            ws.put(ubuf_off);
             ubuf_off = nullptr;
         }
     }
@@ -2534,7 +2532,7 @@ int dev_step1(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, tsg_d
         el ? (double)Ael->nnz * ((double)Bel->nnz / (double)(Bel->m > 0 ? Bel->m : 1))
            : (double)A.numtile * ((double)B.numtile / (double)(B.tilem > 0 ? B.tilem : 1));
     const bool store = bm_bytes <= (4ull << 30) && est_products >= (double)nunits1 * (win / 32) / 8.0;
-    if (store && !ubuf && !(ablate_bits() & 256) && cx.get(&bmst, bm_bytes / 4) != TSG_OK) {
+    if (store && !ubuf && !(ablate_bits() & 256) && ws.get(&bmst, bm_bytes / 4) != TSG_OK) {
         bmst = nullptr;
         (void)hipGetLastError();
     }
@@ -2564,15 +2562,13 @@ int dev_step1(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, tsg_d
         // the caller indexes C tiles in unit-buffer space (tile row i's columns
         // start at ubuf_off[i]): no compaction; C.tile_columnidx is the buffer
         C.tile_columnidx = ubuf;
-        *tbase_out = ubuf_off;
+        *tbase_out = ws.keep(ubuf_off);
         *tslots_out = slots;
-        cx.put(bmst);
-        cx.put(ucnt);
-        cx.put(prod);
         *tile_products_out = tile_products;
+        keep_blocks(ws, C);
         return TSG_OK;
     }
-    TSG_TRY(cx.get(&C.tile_columnidx, nb1));
+    TSG_TRY(ws.get(&C.tile_columnidx, nb1));
     if (tilemA > 0) {
         if (ubuf)
             k_step1_gather<<<grid_for(nunits1, WAVES, 16384), WG, 0, s>>>(ubuf, ubuf_off, ucnt, nunits1,
@@ -2589,12 +2585,8 @@ int dev_step1(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, tsg_d
                                          nwin, win, nullptr, ucnt, C.tile_columnidx, nullptr, nullptr);
     }
     TSG_HIP(hipGetLastError());
-    cx.put(bmst);
-    cx.put(ubuf);
-    cx.put(ubuf_off);
-    cx.put(ucnt);
-    cx.put(prod);
     *tile_products_out = tile_products;
+    keep_blocks(ws, C);
     return TSG_OK;
 }
 
@@ -2623,10 +2615,11 @@ int dev_tilespgemm(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, 
     if (!s1elem && (!A.tile_columnidx || !B.tile_columnidx) && A.numtile > 0 && B.numtile > 0)
         return TSG_ERR_INVALID;  // tile-level step 1 needs both tile structures
     long long tile_products = 0;
+    PoolScope ws(cx);
     // per A entry: its B row's position range (step 1's element walk, the split points)
     int2 *ebnd = nullptr;
     if ((s2elem || s3elem) && Acsr->nnz > 0) {
-        TSG_TRY(cx.get(&ebnd, (size_t)Acsr->nnz + 1));
+        TSG_TRY(ws.get(&ebnd, (size_t)Acsr->nnz + 1));
         if (!s1elem) {  // (element step 1 fills them in its capacity kernel)
             k_entry_bounds<<<grid_for(Acsr->nnz, WG, 16384), WG, 0, s>>>(Acsr->columnindex, Acsr->nnz,
                                                                         Bcsr->rowpointer, ebnd);
@@ -2640,6 +2633,8 @@ int dev_tilespgemm(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, 
     TSG_TRY(dev_step1(cx, A, B, C, &tile_products, s, s1elem ? Acsr : nullptr, s1elem ? Bcsr : nullptr,
                       s1elem ? ebnd : nullptr, (s1elem && !(g_ablate & 8192)) ? &tbase : nullptr, &tslots,
                       s1elem && ebnd));
+    adopt_blocks(ws, C);
+    ws.adopt(tbase);
     const int numblkC = C.numtile;
     const size_t nb1 = (size_t)numblkC + 1;
     if (!tbase) tslots = numblkC;
@@ -2648,16 +2643,16 @@ int dev_tilespgemm(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, 
     int *uoff = nullptr, *urow = nullptr, *unit_rc = nullptr, *unit_rb = nullptr;
     int4 *utab = nullptr;
     const long maxu = (long)numblkC / CH + tilemA + 1;
-    TSG_TRY(cx.get(&uoff, (size_t)tilemA + 1));
-    TSG_TRY(cx.get(&urow, (size_t)maxu));
-    TSG_TRY(cx.get(&utab, (size_t)maxu));
-    TSG_TRY(cx.get(&unit_rc, (size_t)maxu * TM));
-    if (!csr_out) TSG_TRY(cx.get(&C.tile_nnz, nb1));  // CSR path: row counts only, no tile nnz scan
-    TSG_TRY(cx.get(&C.mask, ((size_t)tslots + 1) * CM<TM>::TW));
+    TSG_TRY(ws.get(&uoff, (size_t)tilemA + 1));
+    TSG_TRY(ws.get(&urow, (size_t)maxu));
+    TSG_TRY(ws.get(&utab, (size_t)maxu));
+    TSG_TRY(ws.get(&unit_rc, (size_t)maxu * TM));
+    if (!csr_out) TSG_TRY(ws.get(&C.tile_nnz, nb1));  // CSR path: row counts only, no tile nnz scan
+    TSG_TRY(ws.get(&C.mask, ((size_t)tslots + 1) * CM<TM>::TW));
     // CSR path: step 2 hands step 3 a u16 code per C tile and full masks only for
     // tiles with > 1 nonzero (most webbase-like C tiles hold one nonzero)
     u16 *codeC = nullptr;
-    if (csr_out) TSG_TRY(cx.get(&codeC, (size_t)tslots + 1));
+    if (csr_out) TSG_TRY(ws.get(&codeC, (size_t)tslots + 1));
     k_units_per_row<<<grid_for(tilemA, WG, 4096), WG, 0, s>>>(C.tile_ptr, tilemA, uoff);
     TSG_TRY(scan_exclusive_i32(cx, uoff, (long)tilemA + 1, s));
     k_unit_rows<<<grid_for(tilemA, WG, 4096), WG, 0, s>>>(uoff, C.tile_ptr, tilemA, urow, utab, tbase);
@@ -2666,7 +2661,7 @@ int dev_tilespgemm(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, 
     // element split tables: sizes queued ahead of the unit count's read (one round trip)
     long long *ebase = nullptr;
     if (s2elem || s3elem) {
-        TSG_TRY(cx.get(&ebase, (size_t)tilemA + 1));
+        TSG_TRY(ws.get(&ebase, (size_t)tilemA + 1));
         k_esplit_counts<TM><<<grid_for(tilemA, WG, 4096), WG, 0, s>>>(uoff, Acsr->rowpointer, A.m, tilemA, ebase);
         TSG_TRY(scan_exclusive_i64(cx, ebase, (long)tilemA + 1, s));
     }
@@ -2682,15 +2677,15 @@ int dev_tilespgemm(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, 
     long long *sbase = nullptr;
     int *split = nullptr;
     if (tilepay) {
-        TSG_TRY(cx.get(&sbase, (size_t)tilemA + 1));
+        TSG_TRY(ws.get(&sbase, (size_t)tilemA + 1));
         k_split_counts<<<grid_for(tilemA, WG, 4096), WG, 0, s>>>(uoff, A.tile_ptr, tilemA, sbase);
         TSG_TRY(scan_exclusive_i64(cx, sbase, (long)tilemA + 1, s));
         long long nsplit = 0;
         TSG_TRY(read_i64(cx, sbase + tilemA, &nsplit, s));
-        TSG_TRY(cx.get(&split, (size_t)nsplit + 1));
+        TSG_TRY(ws.get(&split, (size_t)nsplit + 1));
         int *trowA = A.tile_rowidx;
         if (!trowA) {
-            TSG_TRY(cx.get(&trowA, (size_t)A.numtile + 1));
+            TSG_TRY(ws.get(&trowA, (size_t)A.numtile + 1));
             k_crow<<<grid_for(tilemA, WAVES, 8192), WG, 0, s>>>(A.tile_ptr, tilemA, trowA);
         }
         if (A.numtile > 0)
@@ -2698,7 +2693,7 @@ int dev_tilespgemm(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, 
                                                                       A.tile_columnidx, B.tile_ptr, B.tile_columnidx,
                                                                       uoff, C.tile_ptr, C.tile_columnidx, sbase, split);
         TSG_HIP(hipGetLastError());
-        if (trowA != A.tile_rowidx) cx.put(trowA);
+        if (trowA != A.tile_rowidx) ws.put(trowA);
     }
     const ABView V{A.tile_ptr, A.tile_columnidx, A.tile_nnz, A.tile_csr_Col, A.tile_csr_Value,
                    B.tile_ptr, B.tile_columnidx, B.rm_mask, B.rm_rowstart, B.tile_csr_Col, B.tile_csr_Value,
@@ -2708,10 +2703,10 @@ int dev_tilespgemm(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, 
     int *esplit = nullptr;
     int4 *etab = nullptr;
     if (s2elem || s3elem) {
-        TSG_TRY(cx.get(&esplit, (size_t)ne + 1));
+        TSG_TRY(ws.get(&esplit, (size_t)ne + 1));
         E = ECsr{A.m, Acsr->rowpointer, Acsr->columnindex, Acsr->value, Bcsr->rowpointer, Bcsr->columnindex,
                  Bcsr->value, esplit, ebase};
-        TSG_TRY(cx.get(&etab, (size_t)maxu));
+        TSG_TRY(ws.get(&etab, (size_t)maxu));
         if (nunits > 0) {
             k_unit_etab<TM><<<grid_for(nunits, WG, 8192), WG, 0, s>>>(utab, nunits, Acsr->rowpointer, A.m, ebase,
                                                                       etab);
@@ -2742,8 +2737,8 @@ int dev_tilespgemm(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, 
     if (csr_out) {
         csr_out->m = A.m;
         csr_out->n = B.n;
-        TSG_TRY(cx.get(&csr_out->rowpointer, (size_t)A.m + 1));
-        TSG_TRY(cx.get(&unit_rb, (size_t)maxu * TM));
+        TSG_TRY(ws.get(&csr_out->rowpointer, (size_t)A.m + 1));
+        TSG_TRY(ws.get(&unit_rb, (size_t)maxu * TM));
         k_set_i32<<<1, 1, 0, s>>>(csr_out->rowpointer + A.m, 0);
         if (tilemA > 0)
             k_unit_rowbase<TM><<<grid_for((long)tilemA * TM, WG, 8192), WG, 0, s>>>(uoff, tilemA, A.m, unit_rc, unit_rb,
@@ -2761,12 +2756,12 @@ int dev_tilespgemm(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, 
     // ---- step 3 ----
     if (csr_out) {
         csr_out->nnz = nnzC;
-        TSG_TRY(cx.get(&csr_out->columnindex, (size_t)nnzC + 1));
-        TSG_TRY(cx.get(&csr_out->value, (size_t)nnzC + 1));
+        TSG_TRY(ws.get(&csr_out->columnindex, (size_t)nnzC + 1));
+        TSG_TRY(ws.get(&csr_out->value, (size_t)nnzC + 1));
     } else {
-        TSG_TRY(cx.get(&C.tile_csr_Ptr, nb1 * TM));
-        TSG_TRY(cx.get(&C.tile_csr_Col, (size_t)nnzC + 1));
-        TSG_TRY(cx.get(&C.tile_csr_Value, (size_t)nnzC + 1));
+        TSG_TRY(ws.get(&C.tile_csr_Ptr, nb1 * TM));
+        TSG_TRY(ws.get(&C.tile_csr_Col, (size_t)nnzC + 1));
+        TSG_TRY(ws.get(&C.tile_csr_Value, (size_t)nnzC + 1));
     }
     if (ev) TSG_HIP(hipEventRecord(ev[4], s));
     if (csr_out) {
@@ -2813,19 +2808,6 @@ int dev_tilespgemm(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, 
                 "write %.1f gap %.1f  total %.3g\n", 100 * pr[0] / tot, 100 * pr[1] / tot, 100 * pr[2] / tot,
                 100 * pr[3] / tot, 100 * pr[4] / tot, 100 * pr[7] / tot, tot);
     }
-    cx.put(tbase);
-    cx.put(esplit);
-    cx.put(ebase);
-    cx.put(etab);
-    cx.put(codeC);
-    cx.put(ebnd);
-    cx.put(uoff);
-    cx.put(urow);
-    cx.put(utab);
-    cx.put(unit_rc);
-    cx.put(unit_rb);
-    cx.put(split);
-    cx.put(sbase);
     if (ev) TSG_HIP(hipEventRecord(ev[3], s));
     if (defer_nnz) {  // the pipeline's one read-back after step 3
         TSG_HIP(hipMemcpyAsync(cx.pinned, csr_out->rowpointer + A.m, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -2834,6 +2816,8 @@ int dev_tilespgemm(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, 
         C.nnz = nnzC;
         csr_out->nnz = nnzC;
     }
+    keep_blocks(ws, C);
+    if (csr_out) keep_blocks(ws, *csr_out);
     if (st) {
         st->numblkC = numblkC;
         st->nnzC = nnzC;
@@ -2865,9 +2849,11 @@ int dev_tiles_finalize_c(Context &cx, tsg_dev_tiles &C, hipStream_t s, bool zero
     if (zero_empty)
         k_zero_empty_ptr<<<grid_for(C.numtile, WG, 16384), WG, 0, s>>>(C.tile_nnz, C.numtile, C.tile_m, C.tile_csr_Ptr,
                                                                   C.mask);
-    TSG_TRY(cx.get(&C.tile_rowidx, (size_t)C.numtile + 1));
+    PoolScope ws(cx);
+    TSG_TRY(ws.get(&C.tile_rowidx, (size_t)C.numtile + 1));
     k_crow<<<grid_for(C.tilem, WAVES, 8192), WG, 0, s>>>(C.tile_ptr, C.tilem, C.tile_rowidx);
     TSG_HIP(hipGetLastError());
+    ws.keep(C.tile_rowidx);
     return TSG_OK;
 }
 
@@ -2907,17 +2893,19 @@ __global__ __launch_bounds__(WG) void k_build_b_aux(int numtile, int tn, int mw,
 }
 
 int dev_rm2csc_from_structs(Context &cx, tsg_dev_tiles &B, hipStream_t s) {
-    TSG_TRY(cx.get(&B.tile_rm2csc, (size_t)B.numtile + 1));
+    PoolScope ws(cx);
+    TSG_TRY(ws.get(&B.tile_rm2csc, (size_t)B.numtile + 1));
     if (B.numtile > 0)
         k_rm2csc<<<grid_for(B.numtile, WG, 8192), WG, 0, s>>>(B.tile_ptr, B.tile_columnidx, B.csc_tile_ptr,
                                                              B.csc_tile_rowidx, B.tilen, B.numtile, B.tile_rm2csc);
-    TSG_TRY(cx.get(&B.rm_mask, ((size_t)B.numtile + 1) * B.tile_m * (B.tile_n / 16)));
-    TSG_TRY(cx.get(&B.rm_rowstart, ((size_t)B.numtile + 1) * (B.tile_m + 1)));
+    TSG_TRY(ws.get(&B.rm_mask, ((size_t)B.numtile + 1) * B.tile_m * (B.tile_n / 16)));
+    TSG_TRY(ws.get(&B.rm_rowstart, ((size_t)B.numtile + 1) * (B.tile_m + 1)));
     if (B.numtile > 0)
         k_build_b_aux<<<grid_for((long)B.numtile * (2 * B.tile_m + 1), WG, 16384), WG, 0, s>>>(B.numtile, B.tile_m, B.tile_n / 16, B.tile_rm2csc,
                                                                   B.tile_nnz, B.tile_csr_Ptr, B.mask, B.rm_mask,
                                                                   B.rm_rowstart);
     TSG_HIP(hipGetLastError());
+    keep_blocks(ws, B);
     return TSG_OK;
 }
 
@@ -3012,9 +3000,10 @@ int dev_tile2csr(Context &cx, const tsg_dev_tiles &C, tsg_dev_csr &out, hipStrea
     out.m = C.m;
     out.n = C.n;
     out.nnz = C.nnz;
-    TSG_TRY(cx.get(&out.rowpointer, (size_t)C.m + 1));
-    TSG_TRY(cx.get(&out.columnindex, (size_t)C.nnz + 1));
-    TSG_TRY(cx.get(&out.value, (size_t)C.nnz + 1));
+    PoolScope ws(cx);
+    TSG_TRY(ws.get(&out.rowpointer, (size_t)C.m + 1));
+    TSG_TRY(ws.get(&out.columnindex, (size_t)C.nnz + 1));
+    TSG_TRY(ws.get(&out.value, (size_t)C.nnz + 1));
     TSG_HIP(hipMemsetAsync(out.rowpointer, 0, ((size_t)C.m + 1) * sizeof(int), s));
     const int g = grid_for(C.tilem, WAVES, 8192);
     if (C.tilem > 0) {
@@ -3032,6 +3021,7 @@ int dev_tile2csr(Context &cx, const tsg_dev_tiles &C, tsg_dev_csr &out, hipStrea
         else t2c_launch_fill<64>(C, out, g, s);
     }
     TSG_HIP(hipGetLastError());
+    keep_blocks(ws, out);
     return TSG_OK;
 }
 

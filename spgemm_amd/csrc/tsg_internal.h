@@ -46,11 +46,27 @@ class DevicePool {
     void release_all_live();  // returns every live block to the cache
     void trim();              // hipFree of the cached blocks
     size_t bytes_reserved() const { return reserved_; }
+    // diagnostics (tsg_context_pool_stats / tsg_context_fail_alloc)
+    tsg_pool_stats stats() const;
+    void fail_alloc(long long nth) { fail_in_ = nth < 0 ? -1 : nth; }
+    bool fail_pending() const { return fail_in_ >= 0; }
 
   private:
     std::multimap<size_t, void *> free_;
     std::unordered_map<void *, size_t> live_;
     size_t reserved_ = 0;
+    long long allocs_ = 0;
+    long long fail_in_ = -1;  // allocations left before the injected failure (-1: none)
+};
+
+// Run-time knobs of the environment, parsed once at the top of each C-ABI call
+// (per call, not per process: tests switch them inside one process).
+struct Knobs {
+    int force_path = -1;             // TSG_PATH=tiles / band / rows: TSG_PATH_*, else -1 (routed)
+    int step2_mode = -1;             // TSG_STEP2_MODE=elem (1) / tile (0), else -1 (by tile density)
+    bool tiled_csr = true;           // TSG_TILED_CSR=0: tsg_tilespgemm keeps the tile-payload kernels
+    bool rows_checked_scan = false;  // TSG_ROWS_CHECKED_SCAN=1 (tests): the checked scan whatever the size
+    bool dr_per_row = false;         // TSG_DR_PER_ROW (tests): per-row chunks also below DR_GMAX rows
 };
 
 struct Context {
@@ -62,8 +78,8 @@ struct Context {
     long long *dpinned64 = nullptr; //   small results there by system-scope stores)
     hipEvent_t ev[16];
     bool stage_ev = false;         // the stage events too (TSG_STAGE_EVENTS=1), not just the kernel bracket
+    Knobs knobs;                   // the call's run-time knobs (read_knobs, tsg_api.cpp)
     bool ev_ready = false;
-    std::vector<void *> owned;    // outputs handed to the caller (released on reset)
     int init(int dev);
     void destroy();
     template <class T> int get(T **p, size_t count) {
@@ -73,6 +89,58 @@ struct Context {
         return rc;
     }
     void put(void *p) { if (p) pool.release(p); }
+};
+
+// A host function's pool blocks: whatever it got (or adopted) and neither put
+// back early nor kept returns to the pool when the scope ends, so an early
+// return (TSG_TRY / TSG_HIP) leaks nothing.  The pool reuses blocks in stream
+// order on the call's one stream, so a block may return while kernels that
+// read it are still queued, exactly as with an early put().  No heap
+// allocation: a fixed table, sized for the largest user (dev_spgemm16: three
+// tilings of 13 arrays, C, the shares, a plan; dev_rows_run: ~40 arrays) and
+// checked in get().
+class PoolScope {
+  public:
+    static constexpr int kMaxBlocks = 96;
+    explicit PoolScope(Context &cx) : cx_(cx) {}
+    PoolScope(const PoolScope &) = delete;
+    PoolScope &operator=(const PoolScope &) = delete;
+    ~PoolScope() {
+        for (int i = 0; i < n_; ++i) cx_.put(p_[i]);
+    }
+    template <class T> int get(T **p, size_t count) {
+        *p = nullptr;
+        if (n_ == kMaxBlocks) return TSG_ERR_INVALID;
+        TSG_TRY(cx_.get(p, count));
+        p_[n_++] = *p;
+        return TSG_OK;
+    }
+    // a block another function kept for this one (a struct's member) becomes this scope's
+    void adopt(void *p) {
+        if (p && n_ < kMaxBlocks) p_[n_++] = p;
+    }
+    // returns the block now (null, or not this scope's: nothing)
+    void put(void *p) {
+        if (forget(p)) cx_.put(p);
+    }
+    // hands the block out of the scope: an output, or a member of a struct the caller owns
+    template <class T> T *keep(T *p) {
+        forget(p);
+        return p;
+    }
+
+  private:
+    bool forget(void *p) {
+        for (int i = 0; i < n_; ++i)
+            if (p && p_[i] == p) {
+                p_[i] = p_[--n_];
+                return true;
+            }
+        return false;
+    }
+    Context &cx_;
+    void *p_[kMaxBlocks];
+    int n_ = 0;
 };
 
 // ---- launchers implemented in tsg_device.hip (all stream-ordered, no sync) ----
@@ -130,7 +198,7 @@ struct SortedShares {
     int *dflag = nullptr;  // device view of the host flag
 };
 int dev_rows_sorted_shares(Context &cx, const tsg_dev_csr &M, int *host_flag, SortedShares *sh, hipStream_t s);
-int dev_rows_sorted_finish(Context &cx, SortedShares &sh, hipStream_t s);
+int dev_rows_sorted_finish(Context &cx, const SortedShares &sh, hipStream_t s);
 // the same for the B rows A references only (row-merge / band paths)
 int dev_rows_sorted_shares_ref(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, int *host_flag,
                                SortedShares *sh, hipStream_t s);
@@ -146,10 +214,10 @@ struct BandWin {
     long long wcols = 0;         // window columns in all (bounds nnz(C))
     int2 *ebnd = nullptr;        // per A entry: its B row's [start, end) (the statistics kernel's by-product)
 };
-// sh (optional): B's sortedness shares, summed by the check's last kernel (and released)
+// sh (optional): B's sortedness shares, summed by the check's last kernel (the caller releases them after it)
 int dev_band_check(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, bool force, bool *ok, BandWin *bw,
                    hipStream_t s, SortedShares *sh = nullptr);
-int dev_spgemm_band(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, BandWin &bw, tsg_dev_csr &C,
+int dev_spgemm_band(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const BandWin &bw, tsg_dev_csr &C,
                     tsg_stats *st, hipStream_t s, hipEvent_t *ev);
 // row-merge path (tsg_rows.hip): CSR in -> CSR out, B's rows column-sorted;
 // rows binned by element products, each row's B rows merged (or, for the
@@ -180,14 +248,38 @@ constexpr long long kRowsHubProducts = 65536;
 // (peak device memory of the path: 12 B per product of staging + C + the A
 // entry table)
 constexpr long long kRowsProductSizedC = 8LL << 30;
-// sh (optional): B's sortedness shares, summed by the binning kernel (and released)
+// sh (optional): B's sortedness shares, summed by the binning kernel (the caller releases them after it)
 int dev_rows_setup_async(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, RowsPlan &p, hipStream_t s,
                          SortedShares *sh = nullptr);
 void dev_rows_setup_read(Context &cx, RowsPlan &p);  // after the stream synchronised
 bool dev_rows_accept(const RowsPlan &p);
-void dev_rows_release(Context &cx, RowsPlan &p);
+
+// The pool arrays of the structs that pass between host functions, listed once.
+// A function keeps its result's arrays when it succeeds; the caller's scope
+// adopts them (a temporary) or leaves them to the context (an output).
+template <class F> void each_block(tsg_dev_csr &c, F f) { f(c.rowpointer), f(c.columnindex), f(c.value); }
+template <class F> void each_block(tsg_dev_tiles &t, F f) {
+    f(t.tile_ptr), f(t.tile_columnidx), f(t.tile_rowidx), f(t.tile_nnz), f(t.tile_csr_Ptr), f(t.tile_csr_Col),
+        f(t.tile_csr_Value), f(t.mask), f(t.csc_tile_ptr), f(t.csc_tile_rowidx), f(t.tile_rm2csc), f(t.rm_mask),
+        f(t.rm_rowstart);
+}
+template <class F> void each_block(SortedShares &sh, F f) { f(sh.part); }
+template <class F> void each_block(BandWin &bw, F f) { f(bw.win), f(bw.width), f(bw.ebnd); }
+template <class F> void each_block(RowsPlan &p, F f) {
+    f(p.ebnd), f(p.E), f(p.lists), f(p.soff), f(p.cls), f(p.rowpointer);
+}
+template <class S> void keep_blocks(PoolScope &ws, S &st) {
+    each_block(st, [&](void *p) { ws.keep(p); });
+}
+template <class S> void adopt_blocks(PoolScope &ws, S &st) {
+    each_block(st, [&](void *p) { ws.adopt(p); });
+}
+template <class S> void put_blocks(PoolScope &ws, S &st) {  // returns them now and clears the struct
+    each_block(st, [&](void *p) { ws.put(p); });
+    st = S{};
+}
 // ev (optional): 1 set up | 4..5 the row kernels | 3 end
-int dev_rows_run(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, RowsPlan &p, tsg_dev_csr &C,
+int dev_rows_run(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const RowsPlan &p, tsg_dev_csr &C,
                  tsg_stats *st, hipStream_t s, hipEvent_t *ev);
 // two-launch exclusive scans (tsg_rows.hip) for up to 2,048 tiles of 4,096
 // values (TSG_ERR_UNSUPPORTED past it): i64 in place; row pointers (n = m + 1)

@@ -392,15 +392,10 @@ int dev_numeric_plan_create(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr
     if (!shape_ok(A) || !shape_ok(B) || !shape_ok(Cp)) return TSG_ERR_INVALID;
     if (A.n != B.m || Cp.m != A.m || Cp.n != B.n) return TSG_ERR_INVALID;
     const int m = A.m;
+    PoolScope ws(cx);  // (the temporaries: returned to the pool on every way out)
     int *bad = nullptr, *span = nullptr;
     long long *P = nullptr;
-    TSG_TRY(cx.get(&bad, 4));
-    struct Tmp {  // (returned to the pool on every way out)
-        Context &cx;
-        int *&bad, *&span;
-        long long *&P;
-        ~Tmp() { cx.put(bad); cx.put(span); cx.put(P); }
-    } tmp{cx, bad, span, P};
+    TSG_TRY(ws.get(&bad, 4));
     int hbad[2] = {0, 0};
     TSG_HIP(hipMemsetAsync(bad, 0, 4 * sizeof(int), s));
     // 1. row pointers, before anything indexes with them
@@ -424,8 +419,8 @@ int dev_numeric_plan_create(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr
     std::vector<long long> hP((size_t)m);
     std::vector<int> rpC((size_t)m + 1), hspan((size_t)m);
     if (m) {
-        TSG_TRY(cx.get(&P, (size_t)m));
-        TSG_TRY(cx.get(&span, (size_t)m));
+        TSG_TRY(ws.get(&P, (size_t)m));
+        TSG_TRY(ws.get(&span, (size_t)m));
         k_num_rowstats<<<grid_for(m, WAVES, 4096), WG, 0, s>>>(A.rowpointer, A.columnindex, B.rowpointer,
                                                               Cp.rowpointer, Cp.columnindex, m, P, span);
         TSG_HIP(hipGetLastError());

@@ -2496,24 +2496,24 @@ int dev_scan_i64_fused(Context &cx, long long *a, long n, hipStream_t s) {
     const long nt = (n + RS_TILE - 1) / RS_TILE;
     if (n <= 0) return TSG_OK;
     if (nt > RS_INLINE_MAX) return TSG_ERR_UNSUPPORTED;
+    PoolScope ws(cx);
     long long *part = nullptr;
-    TSG_TRY(cx.get(&part, (size_t)nt));
+    TSG_TRY(ws.get(&part, (size_t)nt));
     k_rows_count_sum<long long><<<(unsigned)nt, WG, 0, s>>>(a, n, part);
     k_rows_scan_apply<long long, false><<<(unsigned)nt, WG, 0, s>>>(a, n, part, nullptr, 0, nullptr);
     TSG_HIP(hipGetLastError());
-    cx.put(part);  // (stream-ordered reuse)
-    return TSG_OK;
+    return TSG_OK;  // (part returns here: stream-ordered reuse)
 }
 int dev_scan_rows_fused(Context &cx, int *rp, int m, int *hnnz_dev, hipStream_t s) {
     const long n = (long)m + 1, nt = (n + RS_TILE - 1) / RS_TILE;
     if (nt > RS_INLINE_MAX) return TSG_ERR_UNSUPPORTED;
+    PoolScope ws(cx);
     int *part = nullptr;
-    TSG_TRY(cx.get(&part, (size_t)nt));
+    TSG_TRY(ws.get(&part, (size_t)nt));
     k_rows_count_sum<int><<<(unsigned)nt, WG, 0, s>>>(rp, n, part);
     k_rows_scan_apply<int, true><<<(unsigned)nt, WG, 0, s>>>(rp, n, part, nullptr, m, hnnz_dev);
     TSG_HIP(hipGetLastError());
-    cx.put(part);  // (stream-ordered reuse)
-    return TSG_OK;
+    return TSG_OK;  // (part returns here: stream-ordered reuse)
 }
 
 // Setup (stream-ordered, no host round trip): the entry table, its scan and the
@@ -2523,25 +2523,26 @@ int dev_rows_setup_async(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B
     static_assert(NCLS <= 8, "class counts in cls[0..8)");
     const int m = A.m;
     p = RowsPlan{};
-    TSG_TRY(cx.get(&p.ebnd, (size_t)A.nnz + 1));
-    TSG_TRY(cx.get(&p.E, (size_t)A.nnz + 1));
-    TSG_TRY(cx.get(&p.lists, (size_t)NCLS * (m > 0 ? m : 1)));
-    TSG_TRY(cx.get(&p.soff, (size_t)m + 1));
+    PoolScope ws(cx);
+    TSG_TRY(ws.get(&p.ebnd, (size_t)A.nnz + 1));
+    TSG_TRY(ws.get(&p.E, (size_t)A.nnz + 1));
+    TSG_TRY(ws.get(&p.lists, (size_t)NCLS * (m > 0 ? m : 1)));
+    TSG_TRY(ws.get(&p.soff, (size_t)m + 1));
     // class counts [0..8), 5 u64 statistics [8..18), hub rows' cursors [18..22), the one-walk
     // rows' scratch products (u64) [24..26) and its cursor [26..28)
-    TSG_TRY(cx.get(&p.cls, 32));
-    TSG_TRY(cx.get(&p.rowpointer, (size_t)m + 1));
+    TSG_TRY(ws.get(&p.cls, 32));
+    TSG_TRY(ws.get(&p.rowpointer, (size_t)m + 1));
     unsigned long long *hst = reinterpret_cast<unsigned long long *>(p.cls + 8);
     const long ntile = ((long)A.nnz + 1 + RS_TILE - 1) / RS_TILE;
     if (ntile <= RS_INLINE_MAX) {  // entry table + tile sums, then the apply: two launches
         long long *part = nullptr;
-        TSG_TRY(cx.get(&part, (size_t)ntile));
+        TSG_TRY(ws.get(&part, (size_t)ntile));
         k_rows_entries_sum<<<(unsigned)ntile, WG, 0, s>>>(A.columnindex, A.nnz, B.rowpointer, p.ebnd, p.E, p.cls,
                                                           part);
         k_rows_scan_apply<long long, false><<<(unsigned)ntile, WG, 0, s>>>(p.E, (long)A.nnz + 1, part, nullptr, 0,
                                                                            nullptr);
         TSG_HIP(hipGetLastError());
-        cx.put(part);  // (stream-ordered reuse)
+        ws.put(part);  // (stream-ordered reuse)
     } else {
         k_rows_entries<<<grid_for((long)A.nnz + 1, WG, 16384), WG, 0, s>>>(A.columnindex, A.nnz, B.rowpointer,
                                                                           p.ebnd, p.E, p.cls);
@@ -2553,11 +2554,8 @@ int dev_rows_setup_async(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B
         A.rowpointer, m, p.E, p.E + A.nnz, p.rowpointer, p.lists, p.cls, p.soff, hst, sh ? sh->part : nullptr,
         sh ? sh->nb : 0, sh ? sh->dflag : nullptr);
     TSG_HIP(hipGetLastError());
-    if (sh) {
-        cx.put(sh->part);  // (stream-ordered reuse)
-        *sh = SortedShares{};
-    }
     TSG_HIP(hipMemcpyAsync(cx.pinned64, p.cls, 26 * sizeof(int), hipMemcpyDeviceToHost, s));
+    keep_blocks(ws, p);
     return TSG_OK;
 }
 
@@ -2578,85 +2576,17 @@ void dev_rows_setup_read(Context &cx, RowsPlan &p) {
 // failing (a forced TSG_PATH=rows still returns TSG_ERR_UNSUPPORTED for them)
 bool dev_rows_accept(const RowsPlan &p) { return p.pmax <= 0x7fffffffLL; }
 
-void dev_rows_release(Context &cx, RowsPlan &p) {
-    void *ps[] = {p.ebnd, p.E, p.lists, p.soff, p.cls, p.rowpointer};
-    for (void *q : ps) cx.put(q);
-    p = RowsPlan{};
-}
+// ---- dev_rows_run's state and phases.  Every array below is the run's scope's.
+namespace {
 
-// CSR in -> CSR out from a setup (B's rows column-sorted; the caller checked);
-// consumes the plan.  ev (optional): 1 set up | 4..5 the row kernels | 3 end
-int dev_rows_run(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, RowsPlan &p, tsg_dev_csr &C,
-                 tsg_stats *st, hipStream_t s, hipEvent_t *ev) {
-    const int m = A.m;
-    // (a row's products are counted in int inside the class-H kernels: a row past
-    // 2^31 - 1 products is refused rather than wrapped)
-    if (p.pmax > 0x7fffffffLL) {
-        dev_rows_release(cx, p);
-        return TSG_ERR_UNSUPPORTED;
-    }
-    C = tsg_dev_csr{};
-    C.m = m;
-    C.n = B.n;
-    C.rowpointer = p.rowpointer;
-    p.rowpointer = nullptr;  // (now C's)
-    int2 *ebnd = p.ebnd;
-    long long *E = p.E, *soff = p.soff;
-    int4 *lists = p.lists;
-    const long long products = p.products;
-    int ncls[NCLS];
-    for (int t = 0; t < NCLS; ++t) ncls[t] = p.ncls[t];
-    // (exact row counts first, so that the classes write C in place, measured
-    // slower on webbase twice: round 3's per-row count kernels took 318 us
-    // against the 300 us compaction they save; round 5's several-rows-per-
-    // workgroup LDS hash counts of the merge classes (k_rows_mcount, the staged
-    // S/H rows copied by row) took 326 us, e2e 1.56 vs 1.29 ms --
-    // tools/archive/rows_direct_hashcount.patch; the staging + compaction stays)
-    int *Scol = nullptr;
-    double *Sval = nullptr;
-    TSG_TRY(cx.get(&Scol, (size_t)products + 1));
-    TSG_TRY(cx.get(&Sval, (size_t)products + 1));
-    if (ev && cx.stage_ev) TSG_HIP(hipEventRecord(ev[1], s));
-    if (ev) TSG_HIP(hipEventRecord(ev[4], s));
-#ifdef TSG_ROWS_PROF
-    unsigned long long *dprof = nullptr;
-    TSG_HIP(hipGetSymbolAddress((void **)&dprof, HIP_SYMBOL(g_rows_prof)));
-    TSG_HIP(hipMemsetAsync(dprof, 0, sizeof(unsigned long long) * 3 * 256 * 12, s));
-#endif
-    RowsArgs g{A.rowpointer, A.value, ebnd, E, B.columnindex, B.value, nullptr, 0, C.rowpointer, Scol, Sval};
-    // the classes in turn on the call's stream, heaviest first: class H alone
-    // (its workgroups take a whole CU's LDS and starved behind the short rows'
-    // workgroups when launched beside them), then M4 .. S16.  (The classes on
-    // four streams, forked and joined, measured the same: the phase is bound by
-    // the resident waves' latency chains, and the join cost ~26 us.)
-    auto launch = [&](int c, auto kern, int grid, int nt, hipStream_t st) -> int {
-        if (ncls[c] == 0) return TSG_OK;
-        g.list = lists + (long)c * m;
-        g.nrows = ncls[c];
-        kern<<<grid, nt, 0, st>>>(g);
-        TSG_HIP(hipGetLastError());
-        return TSG_OK;
-    };
-    auto launch_m = [&](int c, auto kern, int grid, int nt, hipStream_t st) -> int {
-        if (ncls[c] == 0) return TSG_OK;
-        g.list = lists + (long)c * m;
-        g.nrows = ncls[c];
-        kern<<<grid, nt, 0, st>>>(g);
-        TSG_HIP(hipGetLastError());
-        return TSG_OK;
-    };
-    // the merge classes are persistent: one resident wave of workgroups
-    if (ncls[7] >= 2 && ncls[7] <= OH_MAX) {
-        k_rows_order_h<<<1, OH_NT, 0, s>>>(E, p.cls, lists + (long)(NCLS - 1) * m);
-        TSG_HIP(hipGetLastError());
-    }
-    int *Oc = nullptr, *Or = nullptr;
-    double *Ox = nullptr;
-    DrRow *drows = nullptr;
-    DrEnt *dents = nullptr;
-    int4 *dchunks = nullptr;
-    int *dord = nullptr;
-    // windowed (W) rows' arrays: per class-H row, per unit, per chunk
+// the hub plan's read-back: what leaves the one-walk kernel
+struct HubSizes {
+    long long wprod = 0, drprod = 0;  // the windowed / the dominant-run rows' products
+    long long ndr = 0;                // dominant-run rows
+    long long nmat = 0;               // the windowed rows' chunk x window offset matrix
+};
+// windowed (W) rows' arrays: per class-H row, per unit, per chunk
+struct WinRows {
     int *wnw = nullptr, *wnch = nullptr, *wlo = nullptr, *wwb = nullptr, *umap = nullptr;
     int *ucnt = nullptr, *ubo = nullptr, *ucount = nullptr, *uoff = nullptr, *ulist = nullptr, *ulist2 = nullptr,
         *lcnt = nullptr;  // (the lists' three sizes packed in one u64, 21 bits each)
@@ -2665,8 +2595,352 @@ int dev_rows_run(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, RowsPl
     int *cbo = nullptr;
     unsigned long long *wst = nullptr;
     int4 *wchunks = nullptr;
-    int nu = 0;
-    long long drnch = 0;  // the dominant-run rows' fill chunks (launched after the row scan)
+    int nu = 0, nc = 0;  // units, chunks
+};
+// hub rows with a dominant run
+struct DomRuns {
+    DrRow *drows = nullptr;
+    DrEnt *dents = nullptr;
+    int4 *dchunks = nullptr;
+    int *dord = nullptr;
+    long long drnch = 0;  // their fill chunks (launched after the row scan)
+};
+// how C is sized, and what the compaction needs of it
+struct CSizing {
+    bool small = false;       // by the products, nnz(C) back with the call's final synchronisation
+    bool fused_scan = false;  // small with at most RS_INLINE_MAX tiles of row counts
+    long rtile = 0;
+    long long nnz = 0, cap = 0;
+    bool lknown = false;    // the windowed fill lists' sizes came back with the checked scan's total
+    int *cfirst = nullptr;  // the compaction's chunk table
+};
+
+// rows past the one-walk kernel (hub rows, more than OW_RUNS runs, or a span
+// that may pass RH_SPAN): the plan sorts them into dominant-run and windowed
+// rows (one more host round trip: sizes of the unit and chunk lists)
+int rows_hub_plan(Context &cx, PoolScope &ws, const RowsArgs &g, int n7, int bn, long long *soff, WinRows &w,
+                  HubSizes &h, hipStream_t s) {
+    TSG_TRY(ws.get(&w.wnw, (size_t)n7 + 1));
+    TSG_TRY(ws.get(&w.wnch, (size_t)n7 + 1));
+    TSG_TRY(ws.get(&w.wlo, (size_t)n7));
+    TSG_TRY(ws.get(&w.wwb, (size_t)n7));
+    TSG_TRY(ws.get(&w.wmat, (size_t)n7 + 1));
+    TSG_TRY(ws.get(&w.wst, 4));
+    TSG_HIP(hipMemsetAsync(w.wst, 0, 4 * sizeof(unsigned long long), s));
+    // (W_UNIT products per unit: 4,096 measured equal, 16,384 / 32,768 slower)
+    k_rows_wplan<<<n7, W_NT, 0, s>>>(g, bn, W_UNIT, w.wnw, w.wnch, w.wlo, w.wwb, w.wmat, w.wst, soff);
+    TSG_HIP(hipGetLastError());
+    TSG_HIP(hipMemsetAsync(w.wnw + n7, 0, sizeof(int), s));
+    TSG_HIP(hipMemsetAsync(w.wnch + n7, 0, sizeof(int), s));
+    TSG_HIP(hipMemsetAsync(w.wmat + n7, 0, sizeof(long long), s));
+    TSG_TRY(scan_exclusive_i32(cx, w.wnw, (long)n7 + 1, s));   // -> ubase
+    TSG_TRY(scan_exclusive_i32(cx, w.wnch, (long)n7 + 1, s));  // -> cbase
+    TSG_TRY(scan_exclusive_i64(cx, w.wmat, (long)n7 + 1, s));  // -> chunk x window offset matrix
+    TSG_HIP(hipMemcpyAsync(cx.pinned64 + 16, w.wst, 3 * sizeof(long long), hipMemcpyDeviceToHost, s));
+    TSG_HIP(hipMemcpyAsync(reinterpret_cast<int *>(cx.pinned64 + 20), w.wnw + n7, sizeof(int),
+                           hipMemcpyDeviceToHost, s));
+    TSG_HIP(hipMemcpyAsync(reinterpret_cast<int *>(cx.pinned64 + 21), w.wnch + n7, sizeof(int),
+                           hipMemcpyDeviceToHost, s));
+    TSG_HIP(hipMemcpyAsync(cx.pinned64 + 22, w.wmat + n7, sizeof(long long), hipMemcpyDeviceToHost, s));
+    TSG_TRY(stream_wait(s));
+    h.wprod = cx.pinned64[16];
+    h.nmat = cx.pinned64[22];
+    h.drprod = cx.pinned64[17];
+    h.ndr = cx.pinned64[18];
+    w.nu = *reinterpret_cast<const int *>(cx.pinned64 + 20);
+    w.nc = *reinterpret_cast<const int *>(cx.pinned64 + 21);
+    return TSG_OK;
+}
+
+// the windowed rows: chunks, units, the units' counts into the row counts
+int rows_win_prepare(PoolScope &ws, const RowsArgs &g, int n7, long long nmat, WinRows &w, hipStream_t s) {
+    const int nu = w.nu, nc = w.nc;
+    const int *ubase = w.wnw, *cbase = w.wnch;
+    TSG_TRY(ws.get(&w.wchunks, (size_t)nc));
+    TSG_TRY(ws.get(&w.cmoff, (size_t)nc));
+    TSG_TRY(ws.get(&w.cbo, (size_t)nmat + 1));
+    TSG_TRY(ws.get(&w.umap, (size_t)nu));
+    TSG_TRY(ws.get(&w.ucnt, (size_t)nu));
+    TSG_TRY(ws.get(&w.ubo, (size_t)nu));
+    TSG_TRY(ws.get(&w.ucount, (size_t)nu));
+    TSG_TRY(ws.get(&w.uoff, (size_t)nu));
+    TSG_TRY(ws.get(&w.urec, (size_t)nu));
+    TSG_TRY(ws.get(&w.ulist, (size_t)nu));
+    TSG_TRY(ws.get(&w.ulist2, (size_t)nu));
+    TSG_TRY(ws.get(&w.lcnt, 2));
+    TSG_HIP(hipMemsetAsync(w.ucnt, 0, (size_t)nu * sizeof(int), s));
+    TSG_HIP(hipMemsetAsync(w.lcnt, 0, 2 * sizeof(int), s));
+    // (the run map of each walk step, not a binary search of the run table
+    // per product: 2.75 vs 3.25 ms on the LiveJournal block)
+    k_rows_wchunks<<<n7, WG, 0, s>>>(g, ubase, cbase, w.wmat, w.wchunks, w.cmoff, w.umap);
+    TSG_HIP(hipGetLastError());
+    k_rows_wcount<<<nc, W_NT, 0, s>>>(g, w.wchunks, w.cmoff, w.wlo, w.wwb, ubase, w.ucnt, w.cbo);
+    TSG_HIP(hipGetLastError());
+    k_rows_wscan<<<n7, W_NT, 0, s>>>(g, ubase, w.ucnt, w.ubo, nullptr, w.urec, w.wlo, w.wwb,
+                                     nu < (1 << 21) ? w.ulist : nullptr, w.ulist2,
+                                     reinterpret_cast<unsigned long long *>(w.lcnt), nu);
+    TSG_HIP(hipGetLastError());
+    k_rows_wscatter<<<nc, W_NT, 0, s>>>(g, w.wchunks, w.cmoff, w.wlo, w.wwb, ubase, w.ubo, w.cbo);
+    TSG_HIP(hipGetLastError());
+    k_rows_wunit<0, WU_NT0><<<nu, WU_NT0, 0, s>>>(g, w.urec, w.ucount, nullptr, nullptr, nullptr, nullptr);
+    TSG_HIP(hipGetLastError());
+    k_rows_wscan<<<n7, W_NT, 0, s>>>(g, ubase, w.ucount, w.uoff, g.rnnz);
+    TSG_HIP(hipGetLastError());
+    return TSG_OK;
+}
+
+#ifdef TSG_W_DUMP
+// (diagnostic) the units by window bits and products
+int rows_w_dump(const WinRows &w, int n7, long long wprod, hipStream_t s) {
+    const int nu = w.nu;
+    std::vector<WUnit> hr(nu);
+    std::vector<int> hc(nu);
+    TSG_HIP(hipMemcpyAsync(hr.data(), w.urec, sizeof(WUnit) * nu, hipMemcpyDeviceToHost, s));
+    TSG_HIP(hipMemcpyAsync(hc.data(), w.ucount, sizeof(int) * nu, hipMemcpyDeviceToHost, s));
+    TSG_TRY(stream_wait(s));
+    long long cnt[19][8] = {}, pr[19][8] = {}, nz[19][8] = {};
+    for (int u = 0; u < nu; ++u) {
+        int b = 0;
+        while (b < 7 && hr[u].n >= (64 << (2 * b))) ++b;
+        cnt[hr[u].wb][b]++;
+        pr[hr[u].wb][b] += hr[u].n;
+        nz[hr[u].wb][b] += hc[u];
+    }
+    fprintf(stderr, "W rows %d units %d chunks %d products %lld\n", n7, nu, w.nc, wprod);
+    for (int wb = 0; wb < 19; ++wb)
+        for (int b = 0; b < 8; ++b)
+            if (cnt[wb][b])
+                fprintf(stderr, "  wb %2d n<%7d units %7lld products %10lld nnz %10lld\n", wb,
+                        b < 7 ? (64 << (2 * b)) : -1, cnt[wb][b], pr[wb][b], nz[wb][b]);
+    return TSG_OK;
+}
+#endif
+
+// hub rows with a dominant run: their tables and exact counts
+// (per_row, TSG_DR_PER_ROW: the per-row chunks also below DR_GMAX rows -- a test of that path)
+int rows_dr_prepare(PoolScope &ws, const RowsArgs &g, int n7, long long *soff, int *cls, const HubSizes &h,
+                    bool per_row, DomRuns &d, hipStream_t s) {
+    const long long ndr = h.ndr, nch = h.drprod / DR_CH + ndr;
+    TSG_TRY(ws.get(&d.drows, (size_t)ndr));
+    TSG_TRY(ws.get(&d.dents, (size_t)ndr * DR_SMAX));
+    TSG_TRY(ws.get(&d.dchunks, (size_t)nch));
+    TSG_TRY(ws.get(&d.dord, (size_t)ndr));
+    const bool grouped = ndr <= DR_GMAX && !per_row;
+    k_rows_dr_prep<<<n7, DR_NT, 0, s>>>(g, soff, d.drows, d.dents, d.dord, d.dchunks, cls + 20, cls + 21, !grouped);
+    TSG_HIP(hipGetLastError());
+    if (grouped) {
+        k_rows_dr_group<<<1, DR_NT, 0, s>>>(d.drows, cls + 21, d.dord, d.dchunks, cls + 20);
+        TSG_HIP(hipGetLastError());
+    }
+    d.drnch = nch;
+    return TSG_OK;
+}
+
+template <class K>
+int rows_launch(RowsArgs &g, const int4 *lists, int m, const int *ncls, int c, K kern, int grid, int nt,
+                hipStream_t s) {
+    if (ncls[c] == 0) return TSG_OK;
+    g.list = lists + (long)c * m;
+    g.nrows = ncls[c];
+    kern<<<grid, nt, 0, s>>>(g);
+    TSG_HIP(hipGetLastError());
+    return TSG_OK;
+}
+
+// the classes below H in turn on the call's stream, heaviest first: class H
+// ran alone before them (its workgroups take a whole CU's LDS and starved
+// behind the short rows' workgroups when launched beside them), then M4 ..
+// S16.  (The classes on four streams, forked and joined, measured the same:
+// the phase is bound by the resident waves' latency chains, and the join cost
+// ~26 us.)  The merge classes are persistent: one resident wave of workgroups.
+int rows_launch_classes(RowsArgs &g, const int4 *lists, int m, const int *ncls, hipStream_t s) {
+    TSG_TRY(rows_launch(g, lists, m, ncls, 6, k_rows_merge<M4_NT, M4_CAP, M4_RUNS>, ncls[6], M4_NT, s));
+    TSG_TRY(rows_launch(g, lists, m, ncls, 5, k_rows_merge<M3_NT, M3_CAP, M3_RUNS>, ncls[5], M3_NT, s));
+    TSG_TRY(rows_launch(g, lists, m, ncls, 4, k_rows_merge<M2_NT, M2_CAP, M2_RUNS>, ncls[4], M2_NT, s));
+    TSG_TRY(rows_launch(g, lists, m, ncls, 3, k_rows_merge<M1_NT, M1_CAP, M1_RUNS>, ncls[3], M1_NT, s));
+    TSG_TRY(rows_launch(g, lists, m, ncls, 2, k_rows_merge<M0_NT, M0_CAP, M0_RUNS>, ncls[2], M0_NT, s));
+    TSG_TRY(rows_launch(g, lists, m, ncls, 1, k_rows_small<64, S64_U>,
+                        (ncls[1] + WAVES * S64_U - 1) / (WAVES * S64_U), WG, s));
+    TSG_TRY(rows_launch(g, lists, m, ncls, 0, k_rows_small<16, S16_U>,
+                        (ncls[0] + 4 * WAVES * S16_U - 1) / (4 * WAVES * S16_U), WG, s));
+    return TSG_OK;
+}
+
+#ifdef TSG_ROWS_PROF
+int rows_prof_report(const unsigned long long *dprof, const int *ncls, hipStream_t s) {
+    static unsigned long long raw[3 * 256 * 12];
+    unsigned long long pr[36] = {};
+    TSG_HIP(hipMemcpyAsync(raw, dprof, sizeof(raw), hipMemcpyDeviceToHost, s));
+    TSG_TRY(stream_wait(s));
+    for (int c = 0; c < 3; ++c)
+        for (int b = 0; b < 256; ++b)
+            for (int k = 0; k < 12; ++k) pr[c * 12 + k] += raw[(c * 256 + b) * 12 + k];
+    static const char *nm[3] = {"H", "M2-M4", "M0-M1"};
+    for (int c = 0; c < 3; ++c) {
+        const int cnt = c == 0 ? ncls[7] : c == 1 ? ncls[4] + ncls[5] + ncls[6] : ncls[2] + ncls[3];
+        fprintf(stderr, "rows %s (%d rows) us/row:", nm[c], cnt);
+        for (int k = 0; k < 12; ++k) fprintf(stderr, " %.2f", cnt ? pr[c * 12 + k] / 100.0 / cnt : 0.0);
+        fprintf(stderr, "\n");
+    }
+    return TSG_OK;
+}
+#endif
+
+// row counts -> row pointers -> C's arrays, with no host round trip: nnz(C)
+// <= products, so when the products fit int32 (and their 12 B each, beside
+// the staging's, stay within kRowsProductSizedC) the result arrays are sized
+// by them and nnz(C) comes back with the call's final synchronisation;
+// otherwise -- or when that allocation fails -- the checked scan reads nnz(C)
+// back first and C is sized exactly.
+int rows_scan_size_c(Context &cx, PoolScope &ws, const RowsPlan &p, int m, const WinRows &w, tsg_dev_csr &C,
+                     CSizing &z, hipStream_t s) {
+    const long long products = p.products;
+    const int nu = w.nu;
+    int *const hnnz = reinterpret_cast<int *>(cx.pinned64 + 15);
+    int *const hl = reinterpret_cast<int *>(cx.pinned64 + 24);  // the fill lists' sizes (a packed u64)
+    if (z.small) {
+        if (z.fused_scan) {
+            // one launch of tile sums, then one apply that also fills the
+            // compaction's chunk table and reports nnz(C) through the
+            // host-mapped pinned64[15] (no copy back)
+            int *part = nullptr;
+            TSG_TRY(ws.get(&part, (size_t)z.rtile));
+            // the apply fills the compaction's chunk table, a row's chunks by
+            // one thread: fine for short rows, serial for hub rows (a 3.5 M-
+            // nonzero LiveJournal row: 1.7 K chunks, ~50 us) -- past 2^20
+            // products in a row, k_rows_cfirst (a thread per chunk) after it
+            if (p.pmax <= (1LL << 20))
+                TSG_TRY(ws.get(&z.cfirst, (size_t)((products + CP_CH - 1) / CP_CH) + 1));
+            k_rows_count_sum<int><<<(unsigned)z.rtile, WG, 0, s>>>(C.rowpointer, (long)m + 1, part);
+            k_rows_scan_apply<int, true><<<(unsigned)z.rtile, WG, 0, s>>>(
+                C.rowpointer, (long)m + 1, part, z.cfirst, m, reinterpret_cast<int *>(cx.dpinned64 + 15));
+            TSG_HIP(hipGetLastError());
+            ws.put(part);  // (stream-ordered reuse)
+        } else {
+            TSG_TRY(scan_exclusive_i32(cx, C.rowpointer, (long)m + 1, s));
+        }
+        if (ws.get(&C.columnindex, (size_t)products + 1) != TSG_OK ||
+            ws.get(&C.value, (size_t)products + 1) != TSG_OK) {
+            ws.put(C.columnindex);
+            C.columnindex = nullptr;
+            z.small = false;  // (the scan's total is read back below)
+            if (z.fused_scan) {
+                TSG_TRY(stream_wait(s));
+                C.nnz = *hnnz;
+            } else {
+                TSG_TRY(read_i32(cx, C.rowpointer + m, &C.nnz, s));
+            }
+            z.nnz = C.nnz;
+        }
+    } else {  // the checked scan (nnz(C) past int32 fails)
+        if (nu > 0 && nu < (1 << 21))  // (the fill lists' sizes come back with the scan's total)
+            TSG_HIP(hipMemcpyAsync(hl, w.lcnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        TSG_TRY(scan_exclusive_i32_total(cx, C.rowpointer, (long)m + 1, s, &z.nnz));
+        z.lknown = nu > 0 && nu < (1 << 21);
+        if (z.nnz > 0x7fffffffLL) return TSG_ERR_OVERFLOW;
+    }
+    z.cap = z.small ? products : z.nnz;
+    if (!z.small) {
+        TSG_TRY(ws.get(&C.columnindex, (size_t)z.cap + 1));
+        TSG_TRY(ws.get(&C.value, (size_t)z.cap + 1));
+    }
+    return TSG_OK;
+}
+
+// the windowed rows' nonzeros straight into C (the compaction skips those rows)
+// and the dominant-run rows' (their counts exact since k_rows_dr_prep)
+int rows_hub_fills(Context &cx, const RowsArgs &g7, const tsg_dev_csr &C, const WinRows &w, const DomRuns &d,
+                   int *cls, bool lknown, hipStream_t s) {
+    const int nu = w.nu;
+    if (nu > 0) {
+        if (lknown) {
+            // the list sizes came back with the checked scan's total: the bitmap
+            // fill over its list (the longest units first), the sort fill over its
+            const unsigned long long pk = *reinterpret_cast<const unsigned long long *>(cx.pinned64 + 24);
+            const int gs = (int)(pk & 0x1fffff), gh = (int)((pk >> 21) & 0x1fffff), gb = gh + (int)(pk >> 42);
+            if (gb > 0)
+                k_rows_wunit<1, WU_NT><<<gb, WU_NT, 0, s>>>(g7, w.urec, w.ucount, w.uoff, C.rowpointer,
+                                                           C.columnindex, C.value, w.ulist2, nu - 1, gh);
+            if (gs > 0)
+                k_rows_wsort<<<gs, WS_NT, 0, s>>>(g7, w.urec, w.ulist, w.uoff, C.rowpointer, C.columnindex,
+                                                  C.value);
+        } else {
+            // (no read-back on this path: a host round trip of its own for the list
+            // sizes, or grids of every unit with the surplus exiting, cost the
+            // heaviest LiveJournal block 0.12-0.18 ms -- the bitmap fill takes all)
+            k_rows_wunit<1, WU_NT><<<nu, WU_NT, 0, s>>>(g7, w.urec, w.ucount, w.uoff, C.rowpointer, C.columnindex,
+                                                       C.value);
+        }
+        TSG_HIP(hipGetLastError());
+    }
+    if (d.drnch > 0) {
+        // (persistent: the grouped chunk count, under drnch, is known on the device only)
+        k_rows_dr_fill<<<(unsigned)std::min<long long>(d.drnch, 1024), DR_NT, 0, s>>>(
+            g7, C.rowpointer, C.columnindex, C.value, d.drows, d.dents, d.dord, d.dchunks, cls + 20);
+        TSG_HIP(hipGetLastError());
+    }
+    return TSG_OK;
+}
+
+// the staged rows' nonzeros into C, by chunks of CP_CH
+int rows_compact(PoolScope &ws, int m, const long long *soff, const int *Scol, const double *Sval,
+                 const tsg_dev_csr &C, CSizing &z, hipStream_t s) {
+    if (z.cap > 0) {
+        const int nch = (int)((z.cap + CP_CH - 1) / CP_CH);
+        if (!z.cfirst) {  // (else the fused scan filled it)
+            TSG_TRY(ws.get(&z.cfirst, (size_t)nch + 1));
+            k_rows_cfirst<<<grid_for(nch, WG, 16384), WG, 0, s>>>(m, C.rowpointer, (long)nch, z.cfirst);
+            TSG_HIP(hipGetLastError());
+        }
+        k_rows_compact<<<nch, WG, 0, s>>>(m, z.cfirst, soff, C.rowpointer, Scol, Sval, C.columnindex, C.value);
+    }
+    TSG_HIP(hipGetLastError());
+    return TSG_OK;
+}
+
+}  // namespace
+
+// CSR in -> CSR out from a setup (B's rows column-sorted; the caller checked).
+// The plan stays the caller's, except its rowpointer array: that becomes C's.
+// ev (optional): 1 set up | 4..5 the row kernels | 3 end
+int dev_rows_run(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const RowsPlan &p, tsg_dev_csr &C,
+                 tsg_stats *st, hipStream_t s, hipEvent_t *ev) {
+    const int m = A.m;
+    // (a row's products are counted in int inside the class-H kernels: a row past
+    // 2^31 - 1 products is refused rather than wrapped)
+    if (p.pmax > 0x7fffffffLL) return TSG_ERR_UNSUPPORTED;
+    C = tsg_dev_csr{};
+    C.m = m;
+    C.n = B.n;
+    C.rowpointer = p.rowpointer;
+    const int *const ncls = p.ncls;
+    const int4 *const lists = p.lists;
+    // (exact row counts first, so that the classes write C in place, measured
+    // slower on webbase twice: round 3's per-row count kernels took 318 us
+    // against the 300 us compaction they save; round 5's several-rows-per-
+    // workgroup LDS hash counts of the merge classes (k_rows_mcount, the staged
+    // S/H rows copied by row) took 326 us, e2e 1.56 vs 1.29 ms --
+    // tools/archive/rows_direct_hashcount.patch; the staging + compaction stays)
+    PoolScope ws(cx);
+    int *Scol = nullptr;
+    double *Sval = nullptr;
+    TSG_TRY(ws.get(&Scol, (size_t)p.products + 1));
+    TSG_TRY(ws.get(&Sval, (size_t)p.products + 1));
+    if (ev && cx.stage_ev) TSG_HIP(hipEventRecord(ev[1], s));
+    if (ev) TSG_HIP(hipEventRecord(ev[4], s));
+#ifdef TSG_ROWS_PROF
+    unsigned long long *dprof = nullptr;
+    TSG_HIP(hipGetSymbolAddress((void **)&dprof, HIP_SYMBOL(g_rows_prof)));
+    TSG_HIP(hipMemsetAsync(dprof, 0, sizeof(unsigned long long) * 3 * 256 * 12, s));
+#endif
+    RowsArgs g{A.rowpointer, A.value, p.ebnd, p.E, B.columnindex, B.value, nullptr, 0, C.rowpointer, Scol, Sval};
+    if (ncls[7] >= 2 && ncls[7] <= OH_MAX) {
+        k_rows_order_h<<<1, OH_NT, 0, s>>>(p.E, p.cls, p.lists + (long)(NCLS - 1) * m);
+        TSG_HIP(hipGetLastError());
+    }
+    HubSizes h;
+    WinRows w;
+    DomRuns d;
     RowsArgs g7 = g;  // (class H's list, for the windowed rows' gather after the row scan)
     if (ncls[7] > 0) {
         // class H: each kernel takes its rows of the class and its other
@@ -2674,299 +2948,59 @@ int dev_rows_run(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, RowsPl
         const int n7 = ncls[7];
         g.list = lists + (long)7 * m;
         g.nrows = n7;
-        long long wprod = 0, drprod = 0, ndr = 0, nmat = 0;
-        int nc = 0;
         g7 = g;
-        // rows past the one-walk kernel (hub rows, more than OW_RUNS runs, or a
-        // span that may pass RH_SPAN): the plan sorts them into dominant-run and
-        // windowed rows (one more host round trip: sizes of the unit and chunk lists)
-        if (p.hubprod > 0 || p.hk > 0 || (long long)B.n > RH_SPAN) {
-            TSG_TRY(cx.get(&wnw, (size_t)n7 + 1));
-            TSG_TRY(cx.get(&wnch, (size_t)n7 + 1));
-            TSG_TRY(cx.get(&wlo, (size_t)n7));
-            TSG_TRY(cx.get(&wwb, (size_t)n7));
-            TSG_TRY(cx.get(&wmat, (size_t)n7 + 1));
-            TSG_TRY(cx.get(&wst, 4));
-            TSG_HIP(hipMemsetAsync(wst, 0, 4 * sizeof(unsigned long long), s));
-            // (W_UNIT products per unit: 4,096 measured equal, 16,384 / 32,768 slower)
-            k_rows_wplan<<<n7, W_NT, 0, s>>>(g, B.n, W_UNIT, wnw, wnch, wlo, wwb, wmat,
-                                             wst, soff);
-            TSG_HIP(hipGetLastError());
-            TSG_HIP(hipMemsetAsync(wnw + n7, 0, sizeof(int), s));
-            TSG_HIP(hipMemsetAsync(wnch + n7, 0, sizeof(int), s));
-            TSG_HIP(hipMemsetAsync(wmat + n7, 0, sizeof(long long), s));
-            TSG_TRY(scan_exclusive_i32(cx, wnw, (long)n7 + 1, s));   // -> ubase
-            TSG_TRY(scan_exclusive_i32(cx, wnch, (long)n7 + 1, s));  // -> cbase
-            TSG_TRY(scan_exclusive_i64(cx, wmat, (long)n7 + 1, s));  // -> chunk x window offset matrix
-            TSG_HIP(hipMemcpyAsync(cx.pinned64 + 16, wst, 3 * sizeof(long long), hipMemcpyDeviceToHost, s));
-            TSG_HIP(hipMemcpyAsync(reinterpret_cast<int *>(cx.pinned64 + 20), wnw + n7, sizeof(int),
-                                   hipMemcpyDeviceToHost, s));
-            TSG_HIP(hipMemcpyAsync(reinterpret_cast<int *>(cx.pinned64 + 21), wnch + n7, sizeof(int),
-                                   hipMemcpyDeviceToHost, s));
-            TSG_HIP(hipMemcpyAsync(cx.pinned64 + 22, wmat + n7, sizeof(long long), hipMemcpyDeviceToHost, s));
-            TSG_TRY(stream_wait(s));
-            wprod = cx.pinned64[16];
-            nmat = cx.pinned64[22];
-            drprod = cx.pinned64[17];
-            ndr = cx.pinned64[18];
-            nu = *reinterpret_cast<const int *>(cx.pinned64 + 20);
-            nc = *reinterpret_cast<const int *>(cx.pinned64 + 21);
-        }
-        if (nu > 0) {  // the windowed rows
-            const int *ubase = wnw, *cbase = wnch;
-            TSG_TRY(cx.get(&wchunks, (size_t)nc));
-            TSG_TRY(cx.get(&cmoff, (size_t)nc));
-            TSG_TRY(cx.get(&cbo, (size_t)nmat + 1));
-            TSG_TRY(cx.get(&umap, (size_t)nu));
-            TSG_TRY(cx.get(&ucnt, (size_t)nu));
-            TSG_TRY(cx.get(&ubo, (size_t)nu));
-            TSG_TRY(cx.get(&ucount, (size_t)nu));
-            TSG_TRY(cx.get(&uoff, (size_t)nu));
-            TSG_TRY(cx.get(&urec, (size_t)nu));
-            TSG_TRY(cx.get(&ulist, (size_t)nu));
-            TSG_TRY(cx.get(&ulist2, (size_t)nu));
-            TSG_TRY(cx.get(&lcnt, 2));
-            TSG_HIP(hipMemsetAsync(ucnt, 0, (size_t)nu * sizeof(int), s));
-            TSG_HIP(hipMemsetAsync(lcnt, 0, 2 * sizeof(int), s));
-            // (the run map of each walk step, not a binary search of the run table
-            // per product: 2.75 vs 3.25 ms on the LiveJournal block)
-            k_rows_wchunks<<<n7, WG, 0, s>>>(g, ubase, cbase, wmat, wchunks, cmoff, umap);
-            TSG_HIP(hipGetLastError());
-            k_rows_wcount<<<nc, W_NT, 0, s>>>(g, wchunks, cmoff, wlo, wwb, ubase, ucnt, cbo);
-            TSG_HIP(hipGetLastError());
-            k_rows_wscan<<<n7, W_NT, 0, s>>>(g, ubase, ucnt, ubo, nullptr, urec, wlo, wwb,
-                                             nu < (1 << 21) ? ulist : nullptr, ulist2,
-                                             reinterpret_cast<unsigned long long *>(lcnt), nu);
-            TSG_HIP(hipGetLastError());
-            k_rows_wscatter<<<nc, W_NT, 0, s>>>(g, wchunks, cmoff, wlo, wwb, ubase, ubo, cbo);
-            TSG_HIP(hipGetLastError());
-            k_rows_wunit<0, WU_NT0><<<nu, WU_NT0, 0, s>>>(g, urec, ucount, nullptr, nullptr, nullptr, nullptr);
-            TSG_HIP(hipGetLastError());
-            k_rows_wscan<<<n7, W_NT, 0, s>>>(g, ubase, ucount, uoff, g.rnnz);
-            TSG_HIP(hipGetLastError());
+        if (p.hubprod > 0 || p.hk > 0 || (long long)B.n > RH_SPAN)
+            TSG_TRY(rows_hub_plan(cx, ws, g, n7, B.n, p.soff, w, h, s));
+        if (w.nu > 0) {
+            TSG_TRY(rows_win_prepare(ws, g, n7, h.nmat, w, s));
 #ifdef TSG_W_DUMP
-            {  // (diagnostic) the units by window bits and products
-                std::vector<WUnit> hr(nu);
-                std::vector<int> hc(nu);
-                TSG_HIP(hipMemcpyAsync(hr.data(), urec, sizeof(WUnit) * nu, hipMemcpyDeviceToHost, s));
-                TSG_HIP(hipMemcpyAsync(hc.data(), ucount, sizeof(int) * nu, hipMemcpyDeviceToHost, s));
-                TSG_TRY(stream_wait(s));
-                long long cnt[19][8] = {}, pr[19][8] = {}, nz[19][8] = {};
-                for (int u = 0; u < nu; ++u) {
-                    int b = 0;
-                    while (b < 7 && hr[u].n >= (64 << (2 * b))) ++b;
-                    cnt[hr[u].wb][b]++;
-                    pr[hr[u].wb][b] += hr[u].n;
-                    nz[hr[u].wb][b] += hc[u];
-                }
-                fprintf(stderr, "W rows %d units %d chunks %d products %lld\n", n7, nu, nc, wprod);
-                for (int w = 0; w < 19; ++w)
-                    for (int b = 0; b < 8; ++b)
-                        if (cnt[w][b])
-                            fprintf(stderr, "  wb %2d n<%7d units %7lld products %10lld nnz %10lld\n", w,
-                                    b < 7 ? (64 << (2 * b)) : -1, cnt[w][b], pr[w][b], nz[w][b]);
-            }
+            TSG_TRY(rows_w_dump(w, n7, h.wprod, s));
 #endif
         }
-        if (p.hprod > wprod + drprod) {  // rows of the one-walk bitmap kernel
+        if (p.hprod > h.wprod + h.drprod) {  // rows of the one-walk bitmap kernel
+            int *Oc = nullptr, *Or = nullptr;
+            double *Ox = nullptr;
             if (p.hbig > 0) {  // one-walk rows past OW_CH products: their scratch
-                TSG_TRY(cx.get(&Oc, (size_t)p.hbig));
-                TSG_TRY(cx.get(&Ox, (size_t)p.hbig));
-                TSG_TRY(cx.get(&Or, (size_t)p.hbig));
+                TSG_TRY(ws.get(&Oc, (size_t)p.hbig));
+                TSG_TRY(ws.get(&Ox, (size_t)p.hbig));
+                TSG_TRY(ws.get(&Or, (size_t)p.hbig));
             }
             k_rows_bitmap<<<n7, RH_NT, 0, s>>>(g, Oc, Ox, Or, reinterpret_cast<unsigned long long *>(p.cls + 26));
             TSG_HIP(hipGetLastError());
         }
-        if (drprod > 0) {  // hub rows with a dominant run
-            const long long nch = drprod / DR_CH + ndr;
-            TSG_TRY(cx.get(&drows, (size_t)ndr));
-            TSG_TRY(cx.get(&dents, (size_t)ndr * DR_SMAX));
-            TSG_TRY(cx.get(&dchunks, (size_t)nch));
-            TSG_TRY(cx.get(&dord, (size_t)ndr));
-            // (TSG_DR_PER_ROW: the per-row chunks also below DR_GMAX rows -- a test of that path)
-            const bool grouped = ndr <= DR_GMAX && !getenv("TSG_DR_PER_ROW");
-            k_rows_dr_prep<<<n7, DR_NT, 0, s>>>(g, soff, drows, dents, dord, dchunks, p.cls + 20, p.cls + 21,
-                                                !grouped);
-            TSG_HIP(hipGetLastError());
-            if (grouped) {
-                k_rows_dr_group<<<1, DR_NT, 0, s>>>(drows, p.cls + 21, dord, dchunks, p.cls + 20);
-                TSG_HIP(hipGetLastError());
-            }
-            drnch = nch;
-        }
+        if (h.drprod > 0) TSG_TRY(rows_dr_prepare(ws, g, n7, p.soff, p.cls, h, cx.knobs.dr_per_row, d, s));
     }
-    auto classes = [&]() -> int {
-        TSG_TRY(launch_m(6, k_rows_merge<M4_NT, M4_CAP, M4_RUNS>, ncls[6], M4_NT, s));
-        TSG_TRY(launch_m(5, k_rows_merge<M3_NT, M3_CAP, M3_RUNS>, ncls[5], M3_NT, s));
-        TSG_TRY(launch_m(4, k_rows_merge<M2_NT, M2_CAP, M2_RUNS>, ncls[4], M2_NT, s));
-        TSG_TRY(launch_m(3, k_rows_merge<M1_NT, M1_CAP, M1_RUNS>, ncls[3], M1_NT, s));
-        TSG_TRY(launch_m(2, k_rows_merge<M0_NT, M0_CAP, M0_RUNS>, ncls[2], M0_NT, s));
-        TSG_TRY(launch(1, k_rows_small<64, S64_U>, (ncls[1] + WAVES * S64_U - 1) / (WAVES * S64_U), WG, s));
-        TSG_TRY(launch(0, k_rows_small<16, S16_U>, (ncls[0] + 4 * WAVES * S16_U - 1) / (4 * WAVES * S16_U), WG, s));
-        return TSG_OK;
-    };
-    // row counts -> row pointers -> C's arrays, with no host round trip: nnz(C)
-    // <= products, so when the products fit int32 (and their 12 B each, beside
-    // the staging's, stay within kRowsProductSizedC) the result arrays are sized
-    // by them and nnz(C) comes back with the call's final synchronisation;
-    // otherwise -- or when that allocation fails -- the checked scan reads nnz(C)
-    // back first and C is sized exactly.
-    long long nnz = 0;  // (C.rowpointer[m] = 0 from the binning kernel)
+    TSG_TRY(rows_launch_classes(g, lists, m, ncls, s));
+    // (the numeric phase: to the class kernels' end, or -- with windowed or
+    // dominant-run rows, whose nonzeros go straight into C after the row
+    // scan -- to the end of those fills, the scan included)
+    const bool fills = w.nu > 0 || d.drnch > 0;
+    if (ev && !fills) TSG_HIP(hipEventRecord(ev[5], s));
+#ifdef TSG_ROWS_PROF
+    TSG_TRY(rows_prof_report(dprof, ncls, s));
+#endif
+    // (C.rowpointer[m] = 0 from the binning kernel)
     // (TSG_ROWS_CHECKED_SCAN=1: the checked scan whatever the size -- tests take
     // the large products' path, with its fill lists, on small ones)
-    const char *cs = getenv("TSG_ROWS_CHECKED_SCAN");
-    bool small = products <= 0x7fffffffLL && products * 12 <= kRowsProductSizedC && !(cs && cs[0] == '1');
-    long long cap = 0;
-    // small with at most RS_INLINE_MAX tiles of row counts: one launch of tile
-    // sums, then one apply that also fills the compaction's chunk table and
-    // reports nnz(C) through the host-mapped pinned64[15] (no copy back)
-    const long rtile = ((long)m + 1 + RS_TILE - 1) / RS_TILE;
-    const bool fused_scan = small && rtile <= RS_INLINE_MAX;
-    int *const hnnz = reinterpret_cast<int *>(cx.pinned64 + 15);
-    int *const hl = reinterpret_cast<int *>(cx.pinned64 + 24);  // the fill lists' sizes (a packed u64)
-    bool lknown = false;
-    int *cfirst = nullptr;
-    auto scan_alloc = [&]() -> int {
-        if (small) {
-            if (fused_scan) {
-                int *part = nullptr;
-                TSG_TRY(cx.get(&part, (size_t)rtile));
-                // the apply fills the compaction's chunk table, a row's chunks by
-                // one thread: fine for short rows, serial for hub rows (a 3.5 M-
-                // nonzero LiveJournal row: 1.7 K chunks, ~50 us) -- past 2^20
-                // products in a row, k_rows_cfirst (a thread per chunk) after it
-                if (p.pmax <= (1LL << 20))
-                    TSG_TRY(cx.get(&cfirst, (size_t)((products + CP_CH - 1) / CP_CH) + 1));
-                k_rows_count_sum<int><<<(unsigned)rtile, WG, 0, s>>>(C.rowpointer, (long)m + 1, part);
-                k_rows_scan_apply<int, true><<<(unsigned)rtile, WG, 0, s>>>(
-                    C.rowpointer, (long)m + 1, part, cfirst, m, reinterpret_cast<int *>(cx.dpinned64 + 15));
-                TSG_HIP(hipGetLastError());
-                cx.put(part);  // (stream-ordered reuse)
-            } else {
-                TSG_TRY(scan_exclusive_i32(cx, C.rowpointer, (long)m + 1, s));
-            }
-            if (cx.get(&C.columnindex, (size_t)products + 1) != TSG_OK ||
-                cx.get(&C.value, (size_t)products + 1) != TSG_OK) {
-                cx.put(C.columnindex);
-                C.columnindex = nullptr;
-                small = false;  // (the scan's total is read back below)
-                if (fused_scan) {
-                    TSG_TRY(stream_wait(s));
-                    C.nnz = *hnnz;
-                } else {
-                    TSG_TRY(read_i32(cx, C.rowpointer + m, &C.nnz, s));
-                }
-                nnz = C.nnz;
-            }
-        } else {  // the checked scan (nnz(C) past int32 fails)
-            if (nu > 0 && nu < (1 << 21))  // (the fill lists' sizes come back with the scan's total)
-                TSG_HIP(hipMemcpyAsync(hl, lcnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-            TSG_TRY(scan_exclusive_i32_total(cx, C.rowpointer, (long)m + 1, s, &nnz));
-            lknown = nu > 0 && nu < (1 << 21);
-            if (nnz > 0x7fffffffLL) return TSG_ERR_OVERFLOW;
-        }
-        cap = small ? products : nnz;
-        if (!small) {
-            TSG_TRY(cx.get(&C.columnindex, (size_t)cap + 1));
-            TSG_TRY(cx.get(&C.value, (size_t)cap + 1));
-        }
-        return TSG_OK;
-    };
-    // the windowed rows' nonzeros straight into C (the compaction skips those rows)
-    // and the dominant-run rows' (their counts exact since k_rows_dr_prep)
-    auto wfill = [&]() -> int {
-        if (nu > 0) {
-            if (lknown) {
-                // the list sizes came back with the checked scan's total: the bitmap
-                // fill over its list (the longest units first), the sort fill over its
-                const unsigned long long pk = *reinterpret_cast<const unsigned long long *>(hl);
-                const int gs = (int)(pk & 0x1fffff), gh = (int)((pk >> 21) & 0x1fffff), gb = gh + (int)(pk >> 42);
-                if (gb > 0)
-                    k_rows_wunit<1, WU_NT><<<gb, WU_NT, 0, s>>>(g7, urec, ucount, uoff, C.rowpointer, C.columnindex,
-                                                               C.value, ulist2, nu - 1, gh);
-                if (gs > 0)
-                    k_rows_wsort<<<gs, WS_NT, 0, s>>>(g7, urec, ulist, uoff, C.rowpointer, C.columnindex, C.value);
-            } else {
-                // (no read-back on this path: a host round trip of its own for the list
-                // sizes, or grids of every unit with the surplus exiting, cost the
-                // heaviest LiveJournal block 0.12-0.18 ms -- the bitmap fill takes all)
-                k_rows_wunit<1, WU_NT><<<nu, WU_NT, 0, s>>>(g7, urec, ucount, uoff, C.rowpointer, C.columnindex,
-                                                           C.value);
-            }
-            TSG_HIP(hipGetLastError());
-        }
-        if (drnch > 0) {
-            // (persistent: the grouped chunk count, under drnch, is known on the device only)
-            k_rows_dr_fill<<<(unsigned)std::min<long long>(drnch, 1024), DR_NT, 0, s>>>(
-                g7, C.rowpointer, C.columnindex, C.value, drows, dents, dord, dchunks, p.cls + 20);
-            TSG_HIP(hipGetLastError());
-        }
-        return TSG_OK;
-    };
-    {
-        TSG_TRY(classes());
-        // (the numeric phase: to the class kernels' end, or -- with windowed or
-        // dominant-run rows, whose nonzeros go straight into C after the row
-        // scan -- to the end of those fills, the scan included)
-        const bool fills = nu > 0 || drnch > 0;
-        if (ev && !fills) TSG_HIP(hipEventRecord(ev[5], s));
-#ifdef TSG_ROWS_PROF
-        {
-            static unsigned long long raw[3 * 256 * 12];
-            unsigned long long pr[36] = {};
-            TSG_HIP(hipMemcpyAsync(raw, dprof, sizeof(raw), hipMemcpyDeviceToHost, s));
-            TSG_TRY(stream_wait(s));
-            for (int c = 0; c < 3; ++c)
-                for (int b = 0; b < 256; ++b)
-                    for (int k = 0; k < 12; ++k) pr[c * 12 + k] += raw[(c * 256 + b) * 12 + k];
-            static const char *nm[3] = {"H", "M2-M4", "M0-M1"};
-            for (int c = 0; c < 3; ++c) {
-                const int cnt = c == 0 ? ncls[7] : c == 1 ? ncls[4] + ncls[5] + ncls[6] : ncls[2] + ncls[3];
-                fprintf(stderr, "rows %s (%d rows) us/row:", nm[c], cnt);
-                for (int k = 0; k < 12; ++k) fprintf(stderr, " %.2f", cnt ? pr[c * 12 + k] / 100.0 / cnt : 0.0);
-                fprintf(stderr, "\n");
-            }
-        }
-#endif
-        TSG_TRY(scan_alloc());
-        TSG_TRY(wfill());
-        if (ev && fills) TSG_HIP(hipEventRecord(ev[5], s));
-        if (cap > 0) {
-            const int nch = (int)((cap + CP_CH - 1) / CP_CH);
-            if (!cfirst) {  // (the fused scan filled it)
-                TSG_TRY(cx.get(&cfirst, (size_t)nch + 1));
-                k_rows_cfirst<<<grid_for(nch, WG, 16384), WG, 0, s>>>(m, C.rowpointer, (long)nch, cfirst);
-                TSG_HIP(hipGetLastError());
-            }
-            k_rows_compact<<<nch, WG, 0, s>>>(m, cfirst, soff, C.rowpointer, Scol, Sval, C.columnindex, C.value);
-        }
-        TSG_HIP(hipGetLastError());
-    }
-    if (small && !fused_scan)
+    CSizing z;
+    z.small = p.products <= 0x7fffffffLL && p.products * 12 <= kRowsProductSizedC && !cx.knobs.rows_checked_scan;
+    z.rtile = ((long)m + 1 + RS_TILE - 1) / RS_TILE;
+    z.fused_scan = z.small && z.rtile <= RS_INLINE_MAX;
+    TSG_TRY(rows_scan_size_c(cx, ws, p, m, w, C, z, s));
+    TSG_TRY(rows_hub_fills(cx, g7, C, w, d, p.cls, z.lknown, s));
+    if (ev && fills) TSG_HIP(hipEventRecord(ev[5], s));
+    TSG_TRY(rows_compact(ws, m, p.soff, Scol, Sval, C, z, s));
+    if (z.small && !z.fused_scan)
         TSG_HIP(hipMemcpyAsync(cx.pinned64 + 15, C.rowpointer + m, sizeof(int), hipMemcpyDeviceToHost, s));
     if (ev && cx.stage_ev) TSG_HIP(hipEventRecord(ev[3], s));
     TSG_TRY(stream_wait(s));
-    if (small) nnz = *hnnz;
-    C.nnz = (int)nnz;
-    cx.put(cfirst);
-    dev_rows_release(cx, p);
-    cx.put(Scol);
-    cx.put(Sval);
-    {
-        void *ws[] = {wnw, wnch, wlo, wwb, wmat, wst, wchunks, cmoff, cbo, umap, ucnt, ubo, ucount, uoff, urec,
-                      ulist, ulist2, lcnt};
-        for (void *q : ws) cx.put(q);
-    }
-    cx.put(Oc);
-    cx.put(Ox);
-    cx.put(Or);
-    cx.put(drows);
-    cx.put(dents);
-    cx.put(dchunks);
-    cx.put(dord);
+    if (z.small) z.nnz = *reinterpret_cast<const int *>(cx.pinned64 + 15);
+    C.nnz = (int)z.nnz;
+    ws.keep(C.columnindex);
+    ws.keep(C.value);
     if (st) {
         st->nnzC = C.nnz;
-        st->tile_products = products;
+        st->tile_products = p.products;
         st->numblkC = -1;
     }
     return TSG_OK;

@@ -224,10 +224,11 @@ int dev_tile_steps23(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B
         return TSG_ERR_UNSUPPORTED;
     if (!B.csc_tile_ptr || !B.csc_tile_rowidx || !B.mask) return TSG_ERR_INVALID;
     const int nt = C.numtile;
-    TSG_TRY(cx.get(&C.tile_rowidx, (size_t)nt + 1));
-    TSG_TRY(cx.get(&C.tile_nnz, (size_t)nt + 1));
-    TSG_TRY(cx.get(&C.tile_csr_Ptr, (size_t)nt * tm + 1));
-    TSG_TRY(cx.get(&C.mask, (size_t)nt * tm * (tm / 16) + 1));
+    PoolScope ws(cx);
+    TSG_TRY(ws.get(&C.tile_rowidx, (size_t)nt + 1));
+    TSG_TRY(ws.get(&C.tile_nnz, (size_t)nt + 1));
+    TSG_TRY(ws.get(&C.tile_csr_Ptr, (size_t)nt * tm + 1));
+    TSG_TRY(ws.get(&C.mask, (size_t)nt * tm * (tm / 16) + 1));
     if (C.tilem > 0) k_tile_crow<<<grid_for(C.tilem, WAVES, 8192), WG, 0, s>>>(C.tile_ptr, C.tilem, C.tile_rowidx);
     TSG_HIP(hipMemsetAsync(C.tile_nnz + nt, 0, sizeof(int), s));
     TSG_HIP(hipGetLastError());
@@ -252,8 +253,8 @@ int dev_tile_steps23(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B
     TSG_TRY(scan_exclusive_i32_total(cx, C.tile_nnz, (long)nt + 1, s, &nnz));
     C.nnz = (int)nnz;
     if (ev) TSG_HIP(hipEventRecord(ev[2], s));
-    TSG_TRY(cx.get(&C.tile_csr_Col, (size_t)nnz + 1));
-    TSG_TRY(cx.get(&C.tile_csr_Value, (size_t)nnz + 1));
+    TSG_TRY(ws.get(&C.tile_csr_Col, (size_t)nnz + 1));
+    TSG_TRY(ws.get(&C.tile_csr_Value, (size_t)nnz + 1));
     g.CCol = C.tile_csr_Col;
     g.CVal = C.tile_csr_Value;
     if (nt > 0 && nnz > 0) {
@@ -266,6 +267,7 @@ int dev_tile_steps23(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B
     }
     TSG_HIP(hipGetLastError());
     if (ev) TSG_HIP(hipEventRecord(ev[3], s));
+    keep_blocks(ws, C);
     return TSG_OK;
 }
 

@@ -9,7 +9,7 @@ import numpy as np
 
 import weakref
 
-from ._lib import DevCSR, NumericInfo, Stats, check, lib
+from ._lib import DevCSR, NumericInfo, PoolStats, Stats, TsgError, check, lib
 
 
 class DeviceCSR:
@@ -128,6 +128,22 @@ class Context:
 
     def reset(self):
         check("tsg_context_reset", lib().tsg_context_reset(self.ptr))
+
+    def pool_stats(self):
+        """The allocator's counters (diagnostics): live_blocks, live_bytes,
+        reserved_bytes, allocs."""
+        st = PoolStats()
+        check("tsg_context_pool_stats", lib().tsg_context_pool_stats(self.ptr, C.byref(st)))
+        return st.as_dict()
+
+    def fail_alloc(self, nth):
+        """Diagnostics: the nth pool allocation from now (0 = the next) fails once
+        with TSG_ERR_OOM; nth < 0 clears it.  Returns whether an earlier
+        injection was still pending (had not fired)."""
+        rc = lib().tsg_context_fail_alloc(self.ptr, nth)
+        if rc < 0:
+            raise TsgError("tsg_context_fail_alloc", rc)
+        return bool(rc)
 
     def spgemm(self, A, B, tile_m=16, tile_n=16, stream=None, b_sorted=False, raw=False):
         """C = A*B device CSR in -> device CSR out.  Returns (DevCSR struct with

@@ -12,6 +12,7 @@ import pytest
 
 from conftest import FIXTURES, GOLDEN
 import _oracle as O
+from _cases import numeric_mixed_case
 from spgemm_amd import _lib, synth
 from spgemm_amd import tilespgemm as T
 
@@ -157,16 +158,7 @@ def test_numeric_fixture_set_is_complete():
 
 # ---------------------------------------------------------------- 2. class binning
 def test_numeric_mixed_classes(ctx):
-    rng = np.random.default_rng(11)
-    n = 5000
-    rows = []
-    for i in range(3000):  # row lengths spread over 0..600 so every class appears
-        L = int(rng.choice([0, 1, 2, 3, 5, 8, 20, 60, 150, 600], p=[.1, .2, .15, .15, .1, .1, .08, .06, .04, .02]))
-        rows.append(np.sort(rng.choice(n, size=L, replace=False)))
-    A = _csr(3000, n, rows)
-    Bm = synth.random_csr(n, 7000, density=0.003, seed=12)
-    B = (Bm[0], Bm[1], Bm[2],
-         np.concatenate([np.sort(Bm[3][Bm[2][i]:Bm[2][i + 1]]) for i in range(n)]).astype(np.int32))
+    A, B = numeric_mixed_case()
     info = _plan_and_check(ctx, A, B, seeds=(5,))
     assert all(c > 0 for c in info["rows_class"]), info
     assert info["split_units"] > 0 and info["b_rows_sorted"] == 1

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import _oracle as O
+from _cases import csr_of_rows as _csr, hub_rows_case
 from spgemm_amd import synth
 from spgemm_amd import tilespgemm as T
 
@@ -27,15 +28,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(autouse=True)
 def rows_path(monkeypatch):
     monkeypatch.setenv("TSG_PATH", "rows")
-
-
-def _csr(m, n, rows):
-    """CSR from a list of per-row column arrays (kept in the given order)"""
-    lens = [len(c) for c in rows]
-    rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-    ci = (np.concatenate(rows) if sum(lens) else np.zeros(0)).astype(np.int32)
-    vv = (np.arange(len(ci)) % 10).astype(np.float64)
-    return m, n, rp, ci, vv
 
 
 def _check(A_, B_=None, aat=False, real=False, seed=0, path=None):
@@ -275,24 +267,7 @@ def test_rows_hub_rows_windowed_and_dominant_run(monkeypatch, checked):
     (k_rows_wsort), the rest by the bitmap fill, longest first."""
     if checked:
         monkeypatch.setenv("TSG_ROWS_CHECKED_SCAN", "1")
-    rng = np.random.default_rng(41)
-    n = 1_500_000
-    nb = 3000
-    Brows = [np.sort(rng.choice(n, size=int(rng.integers(20, 120)), replace=False)) for _ in range(nb - 3)]
-    Brows.append(np.sort(rng.choice(n, size=200_000, replace=False)))  # a hub's long row
-    Brows.append(np.sort(rng.choice(np.arange(1000, 1000 + 150_000), size=90_000, replace=False)))  # narrow
-    Brows.append(np.arange(0, n, 7)[:80_000])
-    B = _csr(nb, n, Brows)
-    arows = [np.sort(rng.choice(nb - 3, size=1500, replace=False)),   # ~100k products, many runs
-             np.array([5, 17, nb - 3]),                                # long run + short ones
-             np.array([nb - 2, nb - 1]),                               # two long runs, colliding
-             np.array([nb - 2])]                                       # one run, one window
-    # class-H rows of a few thousand products over the whole span: windows of
-    # 2^18 columns, units of ~700 / ~1,050 / ~2,300 products (the sort fill's
-    # and the bitmap fill's sizes on either side of 1,024)
-    arows += [np.sort(rng.choice(nb - 3, size=k, replace=False)) for k in (60, 90, 200)]
-    arows += [np.sort(rng.choice(nb - 3, size=5, replace=False)) for _ in range(50)]
-    A = _csr(len(arows), nb, arows)
+    A, B, arows = hub_rows_case()
     blen = np.diff(B[2].astype(np.int64))
     P = np.array([blen[r].sum() for r in arows])
     assert (P[:4] > 65536).all()

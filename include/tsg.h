@@ -86,6 +86,7 @@ typedef struct tsg_stats {
 #define TSG_PATH_BAND 2   /* banded rows: dense LDS window per row */
 #define TSG_PATH_ROWS 3   /* row merge: rows binned by products, B runs merged in LDS */
 #define TSG_PATH_NUMERIC 4 /* numeric-only run on a known C pattern (tsg_dev_numeric_run) */
+#define TSG_PATH_MASKED 5  /* masked run: A*B on a mask's pattern only (tsg_dev_masked_run) */
 
 /* ---------------- library / device ---------------- */
 const char *tsg_version(void);
@@ -166,6 +167,15 @@ int tsg_spgemm_csr(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C,
  * pattern or one that lacks a column of A*B (C->value is then unspecified).
  * stats may be NULL. */
 int tsg_spgemm_csr_numeric(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, tsg_stats *stats);
+
+/* Masked product C<M> = A*B on a structural mask: C->m, n, nnz, rowpointer and
+ * columnindex are the mask (strictly ascending columns per row), C->value
+ * (malloc'd by the caller, nnz doubles) is overwritten with the entries of A*B
+ * at the mask's positions, 0.0 where no product reaches; products elsewhere
+ * are dropped.  mode: TSG_MASKED_AUTO / _ROWS / _DOT (below).  Uploads the
+ * operands, creates a masked plan, runs it once and destroys it.  stats may be
+ * NULL. */
+int tsg_spgemm_csr_masked(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, int mode, tsg_stats *stats);
 
 /* Frees every non-NULL pointer field and zeroes the struct (covers the
  * reference's matrix_destroy, src/csr2tile.h:509-518, and the CSR arrays). */
@@ -307,6 +317,61 @@ int tsg_dev_numeric_run(tsg_context *ctx, tsg_numeric_plan *plan, const double *
                         const double *b_val, double *c_val, void *stream, tsg_stats *stats /*nullable*/);
 /* TSG_ERR_INVALID for a plan that is not alive on ctx (e.g. destroyed twice). */
 int tsg_dev_numeric_plan_destroy(tsg_context *ctx, tsg_numeric_plan *plan);
+
+/* ---- masked SpGEMM: C<M> = A*B computed on the mask's pattern only ----
+ * For callers that want A*B at known positions (triangle counting L*L<L>,
+ * k-truss, clustering coefficients): only the mask's nnz values are computed
+ * and written; the full product is neither formed nor allocated.  The mask is
+ * structural (a CSR pattern); complemented or valued masks and accumulation
+ * into an existing C are not supported.  A plan has the numeric plan's life
+ * cycle: patterns fixed at creation, values per run, device memory of its own
+ * (it survives tsg_context_reset; tsg_context_destroy frees the plans still
+ * alive).
+ * Each row with mask entries runs on one of two legs.  Row-wise: the numeric
+ * plan's kernels over the mask as the C pattern, every element product of the
+ * row walked, those on a column the mask lacks dropped.  Dot: per mask entry
+ * (i, j) the sorted intersection of A's row i with B^T's row j (B^T is built
+ * at plan time).  The dot leg needs A's rows strictly ascending and B free of a
+ * repeated (row, column); the row-wise leg takes unsorted and repeating B rows
+ * as the numeric plan does.  The dot leg uses no atomics and a summation order
+ * fixed by the plan: its values are bit-reproducible from run to run. */
+#define TSG_MASKED_AUTO 0 /* per row: the dot leg when dot_eligible and D_i < P_i (D_i: the sum over the
+                             row's mask entries of min(len A_i, len B^T_j); P_i: its element products) */
+#define TSG_MASKED_ROWS 1 /* every row on the row-wise leg */
+#define TSG_MASKED_DOT 2  /* every row with mask entries on the dot leg (TSG_ERR_INVALID unless dot_eligible) */
+
+typedef struct tsg_masked_plan tsg_masked_plan;
+
+typedef struct tsg_masked_info {
+    long long products;      /* sum over A entries of rowlen_B(col): the full product's work */
+    long long nnzM;          /* mask entries = values a run writes */
+    long long rows_rowwise, rows_dot; /* rows per leg (rows without mask entries are in neither) */
+    long long products_rowwise;       /* element products the row-wise leg walks */
+    long long dot_work;               /* sum over the dot leg's entries of min(len A_i, len B^T_j) */
+    long long dot_units;              /* work units of the dot leg */
+    int a_rows_sorted, b_rows_sorted, b_no_repeats, dot_eligible; /* what the plan found (1 / 0) */
+} tsg_masked_info;
+
+/* Creates a plan for C<Mask> = A*B on the three patterns (value fields ignored;
+ * device arrays the caller keeps alive and unchanged for the plan's life).
+ * Validation is the numeric plan's, on the device before anything indexes with
+ * the patterns: rowpointer[0] == 0, non-decreasing, rowpointer[m] == nnz;
+ * columns in range; the mask's columns strictly ascending per row; A->n ==
+ * B->m, Mask->m == A->m, Mask->n == B->n.  Any violation, an unknown mode, or
+ * TSG_MASKED_DOT on operands that are not dot_eligible returns
+ * TSG_ERR_INVALID and creates no plan (*plan = NULL).  Synchronous. */
+int tsg_dev_masked_plan_create(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B,
+                               const tsg_dev_csr *Mask, int mode, void *stream,
+                               tsg_masked_plan **plan, tsg_masked_info *info /*nullable*/);
+/* c_val[p] := sum_k A(i,k) * B(k,j) for every mask entry p = (i, j), 0.0 where
+ * no product reaches; nothing is written outside c_val[0, nnzM).  Synchronous on
+ * return.  stats (nullable): path = TSG_PATH_MASKED, nnzCub (= products), nnzC
+ * (= nnzM), t_e2e_ms, t_step3_kernel_ms (the gather and both legs' kernels);
+ * the rest as in the numeric run. */
+int tsg_dev_masked_run(tsg_context *ctx, tsg_masked_plan *plan, const double *a_val, const double *b_val,
+                       double *c_val, void *stream, tsg_stats *stats /*nullable*/);
+/* TSG_ERR_INVALID for a plan that is not alive on ctx (e.g. destroyed twice). */
+int tsg_dev_masked_plan_destroy(tsg_context *ctx, tsg_masked_plan *plan);
 
 /* Copies between host and device (stream-ordered, synchronous on return). */
 int tsg_memcpy_h2d(tsg_context *ctx, void *dst, const void *src, size_t bytes, void *stream);

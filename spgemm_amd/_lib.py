@@ -80,6 +80,16 @@ class NumericInfo(C.Structure):
                     split_units=self.split_units, b_rows_sorted=self.b_rows_sorted)
 
 
+class MaskedInfo(C.Structure):
+    """tsg_masked_info, field for field."""
+    _fields_ = [(n, C.c_longlong) for n in ("products", "nnzM", "rows_rowwise", "rows_dot", "products_rowwise",
+                                            "dot_work", "dot_units")] + [
+        (n, C.c_int) for n in ("a_rows_sorted", "b_rows_sorted", "b_no_repeats", "dot_eligible")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PoolStats(C.Structure):
     """tsg_pool_stats, field for field."""
     _fields_ = [(n, C.c_longlong) for n in ("live_blocks", "live_bytes", "reserved_bytes", "allocs")]
@@ -109,6 +119,8 @@ _SIGS = {
                         C.POINTER(Stats)], C.c_int),
     "tsg_spgemm_csr_numeric": ([C.POINTER(SMatrix), C.POINTER(SMatrix), C.POINTER(SMatrix), C.POINTER(Stats)],
                                C.c_int),
+    "tsg_spgemm_csr_masked": ([C.POINTER(SMatrix), C.POINTER(SMatrix), C.POINTER(SMatrix), C.c_int,
+                               C.POINTER(Stats)], C.c_int),
     "tsg_matrix_destroy": ([C.POINTER(SMatrix)], None),
     "tsg_context_create": ([C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "tsg_context_destroy": ([C.c_void_p], C.c_int),
@@ -133,6 +145,11 @@ _SIGS = {
     "tsg_dev_numeric_run": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                              C.POINTER(Stats)], C.c_int),
     "tsg_dev_numeric_plan_destroy": ([C.c_void_p, C.c_void_p], C.c_int),
+    "tsg_dev_masked_plan_create": ([C.c_void_p, C.POINTER(DevCSR), C.POINTER(DevCSR), C.POINTER(DevCSR), C.c_int,
+                                    C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(MaskedInfo)], C.c_int),
+    "tsg_dev_masked_run": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.POINTER(Stats)], C.c_int),
+    "tsg_dev_masked_plan_destroy": ([C.c_void_p, C.c_void_p], C.c_int),
     "tsg_memcpy_h2d": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
     "tsg_memcpy_d2h": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
     "tsg_memcpy_d2d": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),

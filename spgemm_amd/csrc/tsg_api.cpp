@@ -159,13 +159,18 @@ struct tsg_numeric_plan {
     NumericPlan p;
 };
 
+struct tsg_masked_plan {
+    MaskedPlan p;
+};
+
 struct tsg_context {
     Context cx;
     hipStream_t stream = nullptr;  // host-layer leases only (tsg_dev_* take the caller's stream)
-    // numeric plans alive on this context.  Their device memory is their own
-    // (not the pool's: a reset leaves it alone); tsg_context_destroy frees the
-    // ones still here, so a plan never outlives its context.
+    // numeric and masked plans alive on this context.  Their device memory is
+    // their own (not the pool's: a reset leaves it alone); tsg_context_destroy
+    // frees the ones still here, so a plan never outlives its context.
     std::vector<tsg_numeric_plan *> plans;
+    std::vector<tsg_masked_plan *> masked_plans;
 };
 
 // ------------------------------------------------------------------ helpers
@@ -942,6 +947,11 @@ int tsg_context_destroy(tsg_context *ctx) {
         delete pl;
     }
     ctx->plans.clear();
+    for (tsg_masked_plan *pl : ctx->masked_plans) {
+        dev_masked_plan_free(pl->p);
+        delete pl;
+    }
+    ctx->masked_plans.clear();
     ctx->cx.destroy();
     delete ctx;
     return TSG_OK;
@@ -1377,6 +1387,94 @@ int tsg_spgemm_csr_numeric(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatr
                 rc = TSG_ERR_HIP;
         }
         (void)tsg_dev_numeric_plan_destroy(lease.ctx(), plan);
+    }
+    return rc;
+}
+
+// ---- masked product on the mask's pattern only (tsg_masked.hip)
+int tsg_dev_masked_plan_create(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B, const tsg_dev_csr *Mask,
+                               int mode, void *stream, tsg_masked_plan **plan, tsg_masked_info *info) {
+    if (plan) *plan = nullptr;
+    if (!ctx || !A || !B || !Mask || !plan) return TSG_ERR_INVALID;
+    tsg_masked_plan *pl = new tsg_masked_plan();
+    const int rc = dev_masked_plan_create(ctx->cx, *A, *B, *Mask, mode, pl->p, (hipStream_t)stream);
+    if (rc != TSG_OK) {
+        delete pl;
+        return dev_result(rc, stream, plan);
+    }
+    ctx->masked_plans.push_back(pl);
+    if (info) *info = pl->p.info;
+    *plan = pl;
+    return TSG_OK;
+}
+
+int tsg_dev_masked_run(tsg_context *ctx, tsg_masked_plan *plan, const double *a_val, const double *b_val,
+                       double *c_val, void *stream, tsg_stats *stats) {
+    if (!ctx || !plan ||
+        std::find(ctx->masked_plans.begin(), ctx->masked_plans.end(), plan) == ctx->masked_plans.end())
+        return TSG_ERR_INVALID;
+    MaskedPlan &p = plan->p;
+    if ((p.A.nnz && !a_val) || (p.B.nnz && !b_val) || (p.M.nnz && !c_val)) return TSG_ERR_INVALID;
+    Context &cx = ctx->cx;
+    auto h0 = std::chrono::steady_clock::now();
+    TSG_TRY(dev_masked_run(cx, p, a_val, b_val, c_val, (hipStream_t)stream, stats ? cx.ev : nullptr));
+    if (stats) {
+        auto h1 = std::chrono::steady_clock::now();
+        tsg_stats st{};
+        st.numtileA = st.numtileB = st.numblkC = -1;
+        st.nnzCub = p.info.products;
+        st.nnzC = p.info.nnzM;
+        st.path = TSG_PATH_MASKED;
+        st.t_step3_kernel_ms = ev_ms(cx.ev[6], cx.ev[5]);
+        st.t_e2e_ms = std::chrono::duration<double, std::milli>(h1 - h0).count();
+        *stats = st;
+    }
+    return TSG_OK;
+}
+
+int tsg_dev_masked_plan_destroy(tsg_context *ctx, tsg_masked_plan *plan) {
+    if (!ctx || !plan) return TSG_ERR_INVALID;
+    auto it = std::find(ctx->masked_plans.begin(), ctx->masked_plans.end(), plan);
+    if (it == ctx->masked_plans.end()) return TSG_ERR_INVALID;
+    ctx->masked_plans.erase(it);
+    dev_masked_plan_free(plan->p);  // (runs are synchronous: nothing of the plan's is in flight)
+    delete plan;
+    return TSG_OK;
+}
+
+int tsg_spgemm_csr_masked(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, int mode, tsg_stats *stats) {
+    if (!A || !B || !C || A->n != B->m || C->m != A->m || C->n != B->n) return TSG_ERR_INVALID;
+    if (A->nnz < 0 || B->nnz < 0 || C->nnz < 0 || A->m < 0 || B->m < 0) return TSG_ERR_INVALID;
+    if (!A->rowpointer || !B->rowpointer || !C->rowpointer) return TSG_ERR_INVALID;
+    if ((A->nnz && (!A->columnindex || !A->value)) || (B->nnz && (!B->columnindex || !B->value)) ||
+        (C->nnz && (!C->columnindex || !C->value)))
+        return TSG_ERR_INVALID;
+    HostLease lease;
+    TSG_TRY(lease.acquire());
+    Context &cx = lease.cx();
+    hipStream_t s = lease.stream();
+    PoolScope ws(cx);  // (the uploads; what the dev_* calls keep returns with the lease)
+    tsg_dev_csr dA, dB, dC;
+    int rc = upload_csr(ws, A, dA, s);
+    if (rc == TSG_OK) rc = upload_csr(ws, B, dB, s);
+    if (rc == TSG_OK) {
+        dC.m = C->m; dC.n = C->n; dC.nnz = C->nnz;
+        rc = upload(ws, &dC.rowpointer, C->rowpointer, (size_t)C->m + 1, s);
+    }
+    if (rc == TSG_OK) rc = upload(ws, &dC.columnindex, C->columnindex, (size_t)C->nnz, s);
+    if (rc == TSG_OK) rc = ws.get(&dC.value, (size_t)C->nnz + 1);
+    if (rc == TSG_OK && hipStreamSynchronize(s) != hipSuccess) rc = TSG_ERR_HIP;
+    tsg_masked_plan *plan = nullptr;
+    if (rc == TSG_OK) rc = tsg_dev_masked_plan_create(lease.ctx(), &dA, &dB, &dC, mode, s, &plan, nullptr);
+    if (rc == TSG_OK) {
+        rc = tsg_dev_masked_run(lease.ctx(), plan, dA.value, dB.value, dC.value, s, stats);
+        if (rc == TSG_OK && C->nnz) {
+            if (hipMemcpyAsync(C->value, dC.value, (size_t)C->nnz * sizeof(double), hipMemcpyDeviceToHost, s) !=
+                    hipSuccess ||
+                hipStreamSynchronize(s) != hipSuccess)
+                rc = TSG_ERR_HIP;
+        }
+        (void)tsg_dev_masked_plan_destroy(lease.ctx(), plan);
     }
     return rc;
 }

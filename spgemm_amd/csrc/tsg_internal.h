@@ -322,6 +322,9 @@ inline int numeric_row_class(long long len_c, long long products) {
     if (len_c <= kNumWgLen && products <= kNumWgProducts) return 2;
     return 3;
 }
+// one launch's workgroups at most where the grid is a unit count: a grid's threads
+// (workgroups x 256) must stay below 2^32
+constexpr int kMaxGridBlocks = 1 << 23;
 struct NumericPlan {
     tsg_dev_csr A{}, B{}, C{};  // the caller's pattern arrays (values unused)
     void *block = nullptr;      // the plan's own hipMalloc block (not the pool's: survives a reset)
@@ -336,11 +339,53 @@ struct NumericPlan {
     int *hmiss = nullptr;       // its pinned host copy (the run's one D2H copy)
     tsg_numeric_info info{};
 };
+// the plan's validation on its own (synchronous): shapes, row pointers, columns
+// in range, Cp's columns strictly ascending per row; *b_sorted: whether B's are
+int dev_numeric_validate(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &Cp,
+                         bool *b_sorted, hipStream_t s);
+// skip (optional, host, one byte per row): rows with a non-zero byte go to the
+// never-launched list kNumLists whatever their class -- a run leaves their
+// c_val alone (the masked plan's rows of the dot leg).  validated (optional):
+// the caller ran dev_numeric_validate on these patterns and passes what it
+// found for B; null: validated here.
 int dev_numeric_plan_create(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &Cp,
-                            NumericPlan &p, hipStream_t s);
+                            NumericPlan &p, hipStream_t s, const unsigned char *skip = nullptr,
+                            const bool *validated = nullptr);
 int dev_numeric_run(Context &cx, NumericPlan &p, const double *a_val, const double *b_val, double *c_val,
                     hipStream_t s, hipEvent_t *ev, int *missed);
 void dev_numeric_plan_free(NumericPlan &p);
+
+// masked product C<M> = A*B on the mask's pattern only (tsg_masked.hip,
+// DESIGN.md section 3.8).  Each row with mask entries takes one of two legs:
+//   row-wise  an internal NumericPlan over the mask as the C pattern (a product
+//             whose column the mask lacks misses its lookup and is dropped)
+//   dot       per mask entry (i, j) the intersection of A's row i with B^T's
+//             row j; work units of (row, a range of its mask entries)
+// A unit's work -- the sum over its entries of min(len A_i, len B^T_j) -- is at
+// most kMskUnitWork (an entry heavier than that is a unit of its own) and it
+// has at most kMskUnitEntries entries; A rows of at most kMskRowLds entries are
+// copied to LDS.  AUTO sends a row to the dot leg when kMskDotCost * D_i < P_i
+// (D_i: the row's dot work, P_i: its element products).
+constexpr int kMskUnitWork = 4096, kMskUnitEntries = 256, kMskRowLds = 2048;
+constexpr long long kMskDotCost = 1;
+struct MaskedPlan {
+    NumericPlan rows;            // the row-wise leg (the dot leg's rows and the rows without mask entries skipped)
+    tsg_dev_csr A{}, B{}, M{};   // the caller's pattern arrays (values unused)
+    void *block = nullptr;       // the plan's own hipMalloc block: B^T, the gathered values, the units
+    size_t bytes = 0;
+    int *bt_rp = nullptr, *bt_ci = nullptr, *bt_pos = nullptr;  // B^T: row pointers, columns (= B's rows,
+                                                                 //   ascending), each entry's position in B
+    double *bt_val = nullptr;    // b_val in B^T's order, gathered by every run
+    int4 *units = nullptr;       // dot units: (row, first mask entry, entries, -)
+    int nunits = 0;
+    tsg_masked_info info{};
+};
+int dev_masked_plan_create(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &M, int mode,
+                           MaskedPlan &p, hipStream_t s);
+// ev (optional): ev[6] before the first kernel, ev[5] after the last
+int dev_masked_run(Context &cx, MaskedPlan &p, const double *a_val, const double *b_val, double *c_val,
+                   hipStream_t s, hipEvent_t *ev);
+void dev_masked_plan_free(MaskedPlan &p);
 
 // read a device int / long long synchronously through pinned memory
 int read_i32(Context &cx, const int *d, int *h, hipStream_t s);

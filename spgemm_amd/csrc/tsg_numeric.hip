@@ -383,18 +383,12 @@ void dev_numeric_plan_free(NumericPlan &p) {
     p.hmiss = nullptr;
 }
 
-// Synchronous (the one-off cost): validation, then the binning on the host from
-// the per-row products the device counted.  Temporaries come from the pool and
-// go back to it; what the plan keeps is one hipMalloc block of its own.
-int dev_numeric_plan_create(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &Cp,
-                            NumericPlan &p, hipStream_t s) {
-    p = NumericPlan{};
+int dev_numeric_validate(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &Cp,
+                         bool *b_sorted, hipStream_t s) {
     if (!shape_ok(A) || !shape_ok(B) || !shape_ok(Cp)) return TSG_ERR_INVALID;
     if (A.n != B.m || Cp.m != A.m || Cp.n != B.n) return TSG_ERR_INVALID;
-    const int m = A.m;
     PoolScope ws(cx);  // (the temporaries: returned to the pool on every way out)
-    int *bad = nullptr, *span = nullptr;
-    long long *P = nullptr;
+    int *bad = nullptr;
     TSG_TRY(ws.get(&bad, 4));
     int hbad[2] = {0, 0};
     TSG_HIP(hipMemsetAsync(bad, 0, 4 * sizeof(int), s));
@@ -415,6 +409,23 @@ int dev_numeric_plan_create(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr
     TSG_HIP(hipMemcpyAsync(hbad + 1, bad + 1, sizeof(int), hipMemcpyDeviceToHost, s));
     TSG_TRY(stream_wait(s));
     if (hbad[1] || !csorted) return TSG_ERR_INVALID;
+    *b_sorted = bsorted;
+    return TSG_OK;
+}
+
+// Synchronous (the one-off cost): validation, then the binning on the host from
+// the per-row products the device counted.  Temporaries come from the pool and
+// go back to it; what the plan keeps is one hipMalloc block of its own.
+int dev_numeric_plan_create(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &Cp,
+                            NumericPlan &p, hipStream_t s, const unsigned char *skip, const bool *validated) {
+    p = NumericPlan{};
+    bool bsorted = false;
+    if (validated) bsorted = *validated;
+    else TSG_TRY(dev_numeric_validate(cx, A, B, Cp, &bsorted, s));
+    const int m = A.m;
+    PoolScope ws(cx);  // (the temporaries: returned to the pool on every way out)
+    int *span = nullptr;
+    long long *P = nullptr;
     // 3. products per row, classes, lists, units
     std::vector<long long> hP((size_t)m);
     std::vector<int> rpC((size_t)m + 1), hspan((size_t)m);
@@ -446,6 +457,7 @@ int dev_numeric_plan_create(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr
                          : kNumListSplit;
         if (c == 1 && len_c > 0 && hspan[i] <= kNumWindow && hP[i] >= kNumWindowProducts) l = kNumListWaveWin;
         if (c == 0 && len_c == 0 && hP[i] == 0) l = kNumLists;
+        if (skip && skip[i]) l = kNumLists;  // (another leg's row: counted in its class, never launched)
         lst[i] = (unsigned char)l;
         ++p.lcnt[l];
     }
@@ -546,7 +558,10 @@ int dev_numeric_run(Context &cx, NumericPlan &p, const double *a_val, const doub
     const auto n = [&](int l) { return p.lcnt[l]; };
     // (the long rows first: their tails overlap the short rows' kernels)
     if (n(kNumListSplit)) k_num_zero<<<n(kNumListSplit), WG, 0, s>>>(list(kNumListSplit), n(kNumListSplit), p.C.rowpointer, c_val);
-    if (p.nunits) k_num_split<<<p.nunits, WG, 0, s>>>(p.units, o);
+    // (a grid holds fewer than 2^32 threads: past kMaxGridBlocks units -- a LiveJournal-sized pattern's
+    // 3 * 10^7 -- the units go in several launches)
+    for (int u0 = 0; u0 < p.nunits; u0 += kMaxGridBlocks)
+        k_num_split<<<std::min(p.nunits - u0, kMaxGridBlocks), WG, 0, s>>>(p.units + u0, o);
     if (n(kNumListWg)) k_num_rows<WG, kNumWgLen><<<n(kNumListWg), WG, 0, s>>>(list(kNumListWg), n(kNumListWg), o);
     if (n(kNumListWgSmall))
         k_num_rows<WG, kNumWgSmallLen><<<n(kNumListWgSmall), WG, 0, s>>>(list(kNumListWgSmall), n(kNumListWgSmall), o);

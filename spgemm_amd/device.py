@@ -9,7 +9,7 @@ import numpy as np
 
 import weakref
 
-from ._lib import DevCSR, NumericInfo, PoolStats, Stats, TsgError, check, lib
+from ._lib import DevCSR, MaskedInfo, NumericInfo, PoolStats, Stats, TsgError, check, lib
 
 
 class DeviceCSR:
@@ -95,6 +95,59 @@ class NumericPlan:
             pass
 
 
+class MaskedPlan:
+    """A tsg_masked_plan: the entries of A*B at a structural mask's positions
+    only, for fixed patterns and changing values.  Holds the three pattern
+    matrices (their tensors must stay alive and unchanged while the plan lives).
+    The plan's device memory survives Context.reset(); closing the context
+    closes its plans.  The dot leg's values are bit-reproducible from run to
+    run."""
+
+    def __init__(self, ctx, A, B, Mask, mode="auto", stream=None):
+        from .tilespgemm import MASKED_MODES
+        self.ctx, self.A, self.B, self.Mask = ctx, A, B, Mask
+        self.ptr = C.c_void_p()
+        info = MaskedInfo()
+        a, b, c = A.struct(), B.struct(), Mask.struct()
+        s = C.c_void_p(stream) if stream else None
+        check("tsg_dev_masked_plan_create", lib().tsg_dev_masked_plan_create(
+            ctx.ptr, C.byref(a), C.byref(b), C.byref(c), MASKED_MODES.get(mode, mode), s, C.byref(self.ptr),
+            C.byref(info)))
+        self.info = info.as_dict()
+        self.nnzM = Mask.nnz
+
+    def run(self, a_val, b_val, out=None, stream=None, raw=False):
+        """out[0:nnzM] := the entries of A*B at the mask's positions for the f64
+        device tensors a_val / b_val laid on the plan's patterns (0.0 where no
+        product reaches).  Returns (out, stats)."""
+        import torch
+        if not self.ptr:
+            raise RuntimeError("masked plan is closed")
+        for t, n in ((a_val, self.A.nnz), (b_val, self.B.nnz)):
+            if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != n or not t.is_cuda:
+                raise ValueError("values: contiguous float64 device tensors of the patterns' nnz")
+        if out is None:
+            out = torch.empty(self.nnzM, dtype=torch.float64, device=a_val.device)
+        elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != self.nnzM or not out.is_cuda:
+            raise ValueError("out: a contiguous float64 device tensor of nnzM entries")
+        st = Stats()
+        s = C.c_void_p(stream) if stream else None
+        check("tsg_dev_masked_run", lib().tsg_dev_masked_run(
+            self.ctx.ptr, self.ptr, a_val.data_ptr(), b_val.data_ptr(), out.data_ptr(), s, C.byref(st)))
+        return out, (st if raw else st.as_dict())
+
+    def close(self):
+        if self.ptr and self.ctx.ptr:
+            lib().tsg_dev_masked_plan_destroy(self.ctx.ptr, self.ptr)
+        self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """Owns a tsg_context (device, caching allocator, outputs of the last call)."""
 
@@ -117,6 +170,16 @@ class Context:
         containing A*B's pattern).  Raises TsgError (TSG_ERR_INVALID) for a
         malformed pattern."""
         p = NumericPlan(self, A, B, Cpattern, stream)
+        self._plans.add(p)
+        return p
+
+    def masked_plan(self, A, B, Mask, mode="auto", stream=None):
+        """A MaskedPlan for C<Mask> = A*B on the patterns of the DeviceCSRs A, B
+        and Mask (values ignored; the mask's columns strictly ascending per
+        row).  mode: "auto" (per-row choice of leg), "rows" or "dot".  Raises
+        TsgError (TSG_ERR_INVALID) for a malformed pattern, an unknown mode, or
+        "dot" on operands the dot leg cannot take."""
+        p = MaskedPlan(self, A, B, Mask, mode, stream)
         self._plans.add(p)
         return p
 

@@ -14,6 +14,7 @@ kernels of libtsg.so through the C ABI (include/tsg.h):
   tile2csr(C, tm, tn)                                  tile2csr.h:72-140
   spgemm(A, B, tm, tn)               -> (Matrix, stats)  one-shot CSR -> CSR
   spgemm_numeric(A, B, C)            -> stats         values only, on C's known pattern
+  spgemm_masked(A, B, C, mode)       -> stats         A*B at the entries of the mask C only
 
 Errors raise TsgError (the reference exits or silently misbehaves instead).
 """
@@ -29,6 +30,10 @@ _CSR_FIELDS = ("rowpointer", "columnindex", "value")
 # stats["path"]: the CSR-in -> CSR-out route that ran (include/tsg.h TSG_PATH_*)
 PATH_TILES, PATH_BAND, PATH_ROWS = 0, 2, 3  # (1: the retired fused path)
 PATH_NUMERIC = 4  # spgemm_numeric / NumericPlan.run
+PATH_MASKED = 5  # spgemm_masked / MaskedPlan.run
+# masked modes (include/tsg.h TSG_MASKED_*): per-row choice | all rows row-wise | all rows on the dot leg
+MASKED_AUTO, MASKED_ROWS, MASKED_DOT = 0, 1, 2
+MASKED_MODES = {"auto": MASKED_AUTO, "rows": MASKED_ROWS, "dot": MASKED_DOT}
 
 
 def _view(ptr, n, dt):
@@ -166,6 +171,18 @@ def spgemm_numeric(A, B, Cm):
     st = Stats()
     check("tsg_spgemm_csr_numeric", lib().tsg_spgemm_csr_numeric(C.byref(A.s), C.byref(B.s), C.byref(Cm.s),
                                                                  C.byref(st)))
+    return st.as_dict()
+
+
+def spgemm_masked(A, B, Cm, mode="auto"):
+    """Masked product: Cm's rowpointer / columnindex are the mask (strictly
+    ascending columns per row), Cm's values are overwritten with the entries of
+    A*B at the mask's positions (0.0 where no product reaches); products
+    elsewhere are dropped.  mode: "auto", "rows" or "dot" (or a TSG_MASKED_*
+    value).  Returns the stats dict."""
+    st = Stats()
+    check("tsg_spgemm_csr_masked", lib().tsg_spgemm_csr_masked(C.byref(A.s), C.byref(B.s), C.byref(Cm.s),
+                                                               MASKED_MODES.get(mode, mode), C.byref(st)))
     return st.as_dict()
 
 

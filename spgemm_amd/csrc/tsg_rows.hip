@@ -586,21 +586,26 @@ template <int D> __device__ __forceinline__ u32 lane_xor(u32 v) {
     else return (u32)__shfl_xor((int)v, D, 64);
 }
 
+// med3(a, b, 0) = min(a, b) and med3(a, b, ~0u) = max(a, b): a compare-exchange
+// side picked by a selector (per lane or wave-uniform) is one v_med3_u32
+__device__ __forceinline__ u32 minmax_sel(u32 a, u32 b, u32 sel) { return min(max(a, b), max(min(a, b), sel)); }
+// bit B of v spread over the word: 0 or ~0u (one v_bfe_i32)
+template <int B> __device__ __forceinline__ u32 bit_fill(u32 v) { return (u32)((int)(v << (31 - B)) >> 31); }
+constexpr int ilog2_c(int v) { return v <= 1 ? 0 : 1 + ilog2_c(v >> 1); }
+
 // one bitonic stage at element distance J inside sequences of K (elements
 // e = 4*lane + u): ascending where e & K == 0
-// (compare-exchanges whose direction varies by lane: one compare, the
-// direction folded into the lane mask, one select -- instead of min, max and a
-// select per element)
+// (compare-exchanges whose direction varies by lane: a median of three with
+// the lane's 0 / ~0u selector -- no compare, mask and select per element)
 template <int K, int J> __device__ __forceinline__ void bitonic_stage(u32 (&x)[4], int lane) {
     if constexpr (J >= 4) {
         constexpr int D = J / 4;
-        const bool asc = K >= 256 || (lane & (K / 4)) == 0;
-        const bool keep_max = asc != ((lane & D) == 0);
+        // the max goes to the pair's upper lane where ascending, to its lower lane where descending
+        u32 w = (u32)lane;
+        if constexpr (K < 256) w ^= bit_fill<ilog2_c(K / 4)>((u32)lane);
+        const u32 sel = bit_fill<ilog2_c(D)>(w);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const u32 y = lane_xor<D>(x[u]);
-            x[u] = ((y < x[u]) != keep_max) ? y : x[u];
-        }
+        for (int u = 0; u < 4; ++u) x[u] = minmax_sel(x[u], lane_xor<D>(x[u]), sel);
     } else {
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -611,11 +616,10 @@ template <int K, int J> __device__ __forceinline__ void bitonic_stage(u32 (&x)[4
                     x[u] = asc ? lo : hi;
                     x[u + J] = asc ? hi : lo;
                 } else {
-                    const bool desc = (lane & (K / 4)) != 0;
-                    const bool sw = (x[u + J] < x[u]) != desc;
+                    const u32 desc = bit_fill<ilog2_c(K / 4)>((u32)lane);
                     const u32 a = x[u], b = x[u + J];
-                    x[u] = sw ? b : a;
-                    x[u + J] = sw ? a : b;
+                    x[u] = minmax_sel(a, b, desc);
+                    x[u + J] = minmax_sel(a, b, ~desc);
                 }
             }
     }
@@ -629,8 +633,64 @@ template <int K> __device__ __forceinline__ void bitonic_sort(u32 (&x)[4], int l
     bitonic_merge<K, K / 2>(x, lane);
 }
 // a wave's 256 keys ascending in registers, lane l holding elements 4l..4l+3
-// (36 compare-exchange stages, 21 of them across lanes; no LDS, no barrier)
-__device__ __forceinline__ void wave_sort256(u32 (&x)[4], int lane) { bitonic_sort<256>(x, lane); }
+// (36 compare-exchange stages, 21 of them across lanes; no LDS, no barrier).
+// live (wave-uniform): the wave's keys other than the ~0u padding, which fill
+// its first positions.  Where they fit the first 64 (128) positions, the
+// sorted block 0 followed by padding is already ascending: the levels above
+// are skipped (15, 8 stages).
+__device__ __forceinline__ void wave_sort256(u32 (&x)[4], int lane, int live) {
+    bitonic_sort<64>(x, lane);
+    if (live > 64) bitonic_merge<128, 64>(x, lane);
+    if (live > 128) bitonic_merge<256, 128>(x, lane);
+}
+
+// the waves' sorted segments of 256 merged by the rest of a bitonic sort over
+// npow keys (P keys, then ~0u padding), every sequence ascending: per level K
+// the first stage pairs each position with its mirror in the K-block
+// (e ^ (K-1)), the stages at distances K/4 .. 256 pair across waves through
+// LDS (uint4 per lane, the two key buffers kb and kb + STRIDE in turn, one
+// barrier each), the last eight stay in registers.  Wave wv holds positions
+// e0 = 256 wv + 4 lane .. e0 + 3 in x; buffer 0 holds the live waves'
+// segments (a barrier since).  Returns the buffer with the sorted keys.
+//
+// All comparators ascend and the padding is the largest key in a suffix, so
+// positions >= P hold ~0u before and after every stage: a wave at or past P
+// only joins the barriers (its segment of either buffer is neither written
+// nor read), and a live wave whose partner segment is such a wave's -- always
+// the upper one -- keeps its keys without the read.
+template <int STRIDE>
+__device__ __forceinline__ int xwave_merge(u32 (&x)[4], u32 *kb, int lane, int wv, int P, int npow) {
+    constexpr int SEG = 256;
+    wv = __builtin_amdgcn_readfirstlane(wv);
+    npow = __builtin_amdgcn_readfirstlane(npow);
+    const int nlive = (__builtin_amdgcn_readfirstlane(P) + SEG - 1) / SEG;  // the waves holding keys
+    const bool live = wv < nlive;
+    const int e0 = wv * SEG + 4 * lane;
+    int src = 0;
+    // against partner wave pw's four keys at off: the lower wave keeps the min
+    auto cmpx = [&](int pw, int off, bool rev) {
+        if (pw >= nlive) return;
+        const uint4 y = *reinterpret_cast<const uint4 *>(kb + src * STRIDE + off);
+        const u32 yy[4] = {rev ? y.w : y.x, rev ? y.z : y.y, rev ? y.y : y.z, rev ? y.x : y.w};
+        const u32 sel = pw < wv ? ~0u : 0u;  // (wave-uniform)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) x[u] = minmax_sel(x[u], yy[u], sel);
+    };
+    for (int K = 2 * SEG; K <= npow; K <<= 1) {  // (workgroup-uniform)
+        if (live) cmpx(wv ^ (K / SEG - 1), e0 ^ (K - 4), true);
+        for (int J = K >> 2; J >= SEG; J >>= 1) {
+            src ^= 1;
+            if (live) *reinterpret_cast<uint4 *>(kb + src * STRIDE + e0) = make_uint4(x[0], x[1], x[2], x[3]);
+            __syncthreads();
+            if (live) cmpx(wv ^ (J / SEG), e0 ^ J, false);
+        }
+        if (live) bitonic_merge<256, 128>(x, lane);
+        src ^= 1;
+        if (live) *reinterpret_cast<uint4 *>(kb + src * STRIDE + e0) = make_uint4(x[0], x[1], x[2], x[3]);
+        __syncthreads();
+    }
+    return src;
+}
 
 // ---- classes M0..M4: a row's runs sorted into one column-ordered sequence in
 // LDS.  NT threads per row, at most CAP products and RUNS A entries (so a
@@ -773,8 +833,12 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 8 : 1) void k_rows_merge(RowsArgs 
             if (ne > 0) {
                 reinterpret_cast<double4 *>(V)[e0 >> 2] = make_double4(xv[0], xv[1], xv[2], xv[3]);
             }
-            if (wv * SEG < P) wave_sort256(x, lane);  // (wave-uniform)
-            if (wv * SEG < npow) *reinterpret_cast<uint4 *>(kp[0][0] + e0) = make_uint4(x[0], x[1], x[2], x[3]);
+            // (wave-uniform; the waves at or past P hold padding alone: nothing to sort or store)
+            const int live = __builtin_amdgcn_readfirstlane(P - wv * SEG);
+            if (live > 0) {
+                wave_sort256(x, lane, live);
+                *reinterpret_cast<uint4 *>(kp[0][0] + e0) = make_uint4(x[0], x[1], x[2], x[3]);
+            }
         } else {
 #pragma unroll
             for (int u = 0; u < 4; ++u)
@@ -786,33 +850,7 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 8 : 1) void k_rows_merge(RowsArgs 
         __syncthreads();
         RP(1);
         int src = 0;  // packed: the key buffer holding the (merged) keys
-        if (packed) {
-            // the waves' sorted segments merged by the rest of a bitonic sort over
-            // npow keys, every sequence ascending: per level K the first stage pairs
-            // each position with its mirror in the K-block (e ^ (K-1)), the stages
-            // at distances K/4 .. 256 pair across waves through LDS (uint4 per
-            // lane, the two key buffers in turn, one barrier each), the last eight
-            // stay in registers.
-            const bool act = wv * SEG < npow;  // (wave-uniform)
-            auto cmpx = [&](const uint4 y, bool rev, bool keep_min) {
-                const u32 yy[4] = {rev ? y.w : y.x, rev ? y.z : y.y, rev ? y.y : y.z, rev ? y.x : y.w};
-#pragma unroll
-                for (int u = 0; u < 4; ++u) x[u] = keep_min ? min(x[u], yy[u]) : max(x[u], yy[u]);
-            };
-            for (int K = 2 * SEG; K <= npow; K <<= 1) {  // (workgroup-uniform)
-                if (act) cmpx(*reinterpret_cast<const uint4 *>(kp[0][src] + (e0 ^ (K - 4))), true, (e0 & (K >> 1)) == 0);
-                for (int J = K >> 2; J >= SEG; J >>= 1) {
-                    src ^= 1;
-                    if (act) *reinterpret_cast<uint4 *>(kp[0][src] + e0) = make_uint4(x[0], x[1], x[2], x[3]);
-                    __syncthreads();
-                    if (act) cmpx(*reinterpret_cast<const uint4 *>(kp[0][src] + (e0 ^ J)), false, (e0 & J) == 0);
-                }
-                if (act) bitonic_merge<256, 128>(x, lane);
-                src ^= 1;
-                if (act) *reinterpret_cast<uint4 *>(kp[0][src] + e0) = make_uint4(x[0], x[1], x[2], x[3]);
-                __syncthreads();
-            }
-        }
+        if (packed) src = xwave_merge<CAP>(x, kp[0][0], lane, wv, P, npow);
         // unpacked rows: merge-path rounds from the runs; thread t owns
         // [t*ipt, t*ipt + ipt) of every round
         const int ipt = ((P + NT - 1) / NT) | 1;
@@ -1979,31 +2017,16 @@ __global__ __launch_bounds__(WS_NT) void k_rows_wsort(RowsArgs g, const WUnit *u
     const long long o0 = (long long)Crp[R.row] + uoff[u];
     int npow = SEG;  // the sort's length: n padded to a power of two (~0u keys)
     while (npow < n) npow <<= 1;
-    const bool act = wv * SEG < npow;  // (wave-uniform)
     if (e0 < n) reinterpret_cast<double4 *>(V)[tid] = make_double4(xv[0], xv[1], xv[2], xv[3]);
-    if (wv * SEG < n) wave_sort256(x, lane);
-    if (act) *reinterpret_cast<uint4 *>(kb[0] + e0) = make_uint4(x[0], x[1], x[2], x[3]);
-    __syncthreads();
-    int src = 0;
-    auto cmpx = [&](const uint4 y, bool rev, bool keep_min) {
-        const u32 yy[4] = {rev ? y.w : y.x, rev ? y.z : y.y, rev ? y.y : y.z, rev ? y.x : y.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x[k] = keep_min ? min(x[k], yy[k]) : max(x[k], yy[k]);
-    };
-    for (int K = 2 * SEG; K <= npow; K <<= 1) {  // (workgroup-uniform)
-        if (act) cmpx(*reinterpret_cast<const uint4 *>(kb[src] + (e0 ^ (K - 4))), true, (e0 & (K >> 1)) == 0);
-        for (int J = K >> 2; J >= SEG; J >>= 1) {
-            src ^= 1;
-            if (act) *reinterpret_cast<uint4 *>(kb[src] + e0) = make_uint4(x[0], x[1], x[2], x[3]);
-            __syncthreads();
-            if (act) cmpx(*reinterpret_cast<const uint4 *>(kb[src] + (e0 ^ J)), false, (e0 & J) == 0);
-        }
-        if (act) bitonic_merge<256, 128>(x, lane);
-        src ^= 1;
-        if (act) *reinterpret_cast<uint4 *>(kb[src] + e0) = make_uint4(x[0], x[1], x[2], x[3]);
-        __syncthreads();
+    // (wave-uniform; the waves at or past n hold padding alone: nothing to sort or store)
+    const int live = __builtin_amdgcn_readfirstlane(n - wv * SEG);
+    if (live > 0) {
+        wave_sort256(x, lane, live);
+        *reinterpret_cast<uint4 *>(kb[0] + e0) = make_uint4(x[0], x[1], x[2], x[3]);
     }
-    const u32 *const ks = kb[src];  // the sorted keys (positions >= n: ~0u)
+    __syncthreads();
+    const int src = xwave_merge<WS_CAP>(x, kb[0], lane, wv, n, npow);
+    const u32 *const ks = kb[src];  // the sorted keys (positions < n)
     // heads: the first position of each column; their ranks by a workgroup scan
     u32 prev = e0 > 0 && e0 - 1 < n ? ks[e0 - 1] >> IB : ~0u;
     bool hd[4];

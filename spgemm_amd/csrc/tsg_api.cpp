@@ -1,6 +1,6 @@
 // tsg_api.cpp -- C ABI of libtsg.so (include/tsg.h): context + caching device
 // allocator, the reference-named host functions, and the Matrix-Market reader.
-// All arithmetic of the hot path runs in the HIP kernels of tsg_device.hip; the
+// All arithmetic of the hot path runs in the HIP kernels of the .hip files; the
 // host functions only move data and orchestrate.
 #include <hip/hip_runtime.h>
 
@@ -103,10 +103,8 @@ void DevicePool::trim() {
 int Context::init(int dev) {
     device = dev;
     TSG_HIP(hipSetDevice(dev));
-    TSG_HIP(hipHostMalloc((void **)&pinned, 64, hipHostMallocDefault));
-    TSG_HIP(hipHostMalloc((void **)&pinned64, 256, hipHostMallocDefault));
-    TSG_HIP(hipHostGetDevicePointer((void **)&dpinned, pinned, 0));
-    TSG_HIP(hipHostGetDevicePointer((void **)&dpinned64, pinned64, 0));
+    TSG_HIP(hipHostMalloc((void **)&slots, sizeof(HostSlots), hipHostMallocDefault));
+    TSG_HIP(hipHostGetDevicePointer((void **)&dslots, slots, 0));
     for (auto &e : ev) TSG_HIP(hipEventCreate(&e));
     ev_ready = true;
     return TSG_OK;
@@ -133,10 +131,8 @@ void Context::destroy() {
     (void)hipDeviceSynchronize();
     pool.release_all_live();
     pool.trim();
-    if (pinned) (void)hipHostFree(pinned);
-    if (pinned64) (void)hipHostFree(pinned64);
-    pinned = nullptr;
-    pinned64 = nullptr;
+    if (slots) (void)hipHostFree(slots);
+    slots = dslots = nullptr;
     if (ev_ready)
         for (auto &e : ev) (void)hipEventDestroy(e);
     ev_ready = false;
@@ -843,7 +839,7 @@ int tsg_tilespgemm(tsg_smatrix *A, tsg_smatrix *B, tsg_smatrix *C, unsigned int 
         // miss nnz(C): the CSR disagrees with the tiles it was passed with (same
         // counts, other columns) -- C of the tile payloads after all, as from the
         // reference, the payloads' copies inside the timed region (this call's work)
-        if (rc == TSG_OK && cx.pinned[8] != 0) {
+        if (rc == TSG_OK && cx.slots->ctiles_fail != 0) {
             use_csr = false;
             evi[0] = 0, evi[1] = 1, evi[2] = 2, evi[3] = 3;
             t_s1 = -1.0;
@@ -1074,11 +1070,11 @@ static int dev_spgemm16(Context &cx, const tsg_dev_csr *A, const tsg_dev_csr *B,
     // re-checks all of B below.)
     const bool ref_check = b_sorted != 1 && (long long)A->nnz * 64 < (long long)B->m;
     if (b_sorted == 1)
-        cx.pinned[1] = 0;  // (known: no check, no shares for the binning kernel to sum)
+        cx.slots->b_unsorted = 0;  // (known: no check, no shares for the binning kernel to sum)
     else if (ref_check)
-        TSG_TRY(dev_rows_sorted_shares_ref(cx, *A, *B, cx.pinned + 1, &shares, s));
+        TSG_TRY(dev_rows_sorted_shares_ref(cx, *A, *B, &cx.slots->b_unsorted, &shares, s));
     else
-        TSG_TRY(dev_rows_sorted_shares(cx, *B, cx.pinned + 1, &shares, s));
+        TSG_TRY(dev_rows_sorted_shares(cx, *B, &cx.slots->b_unsorted, &shares, s));
     adopt_blocks(ws, shares);
     // Routing, B's rows column-sorted:
     //  * banded path (tsg_band.hip) when A averages >= 8 entries per row and every
@@ -1106,7 +1102,7 @@ static int dev_spgemm16(Context &cx, const tsg_dev_csr *A, const tsg_dev_csr *B,
             put_blocks(ws, shares);  // (stream-ordered reuse)
             adopt_blocks(ws, bw);
         }
-        if (band && cx.pinned[1] != 0) {  // unsorted B rows: the windows mean nothing
+        if (band && cx.slots->b_unsorted != 0) {  // unsorted B rows: the windows mean nothing
             put_blocks(ws, bw);
             band = false;
         }
@@ -1127,7 +1123,7 @@ static int dev_spgemm16(Context &cx, const tsg_dev_csr *A, const tsg_dev_csr *B,
             adopt_blocks(ws, plan);
             TSG_TRY(stream_wait(s));
             dev_rows_setup_read(cx, plan);
-            const bool bsorted0 = cx.pinned[1] == 0;
+            const bool bsorted0 = cx.slots->b_unsorted == 0;
             if (bsorted0 && !force_band && (force_rows || dev_rows_accept(plan))) {
                 TSG_TRY(dev_rows_run(cx, *A, *B, plan, *C, &st, s, evp));
                 plan.rowpointer = nullptr;  // (now C's, and the scope's still)
@@ -1179,7 +1175,7 @@ static int dev_spgemm16(Context &cx, const tsg_dev_csr *A, const tsg_dev_csr *B,
     const double skip = forced == 1 ? 1e300 : forced == 0 ? 0.0 : kStep2ElemMaxTileDensity;
     TSG_TRY(dev_tile_structure(cx, *A, tm, tn, tA, s, skip));  // synchronises the stream
     adopt_blocks(ws, tA);
-    const bool bsorted = cx.pinned[1] == 0;
+    const bool bsorted = cx.slots->b_unsorted == 0;
     const bool alias = A->rowpointer == B->rowpointer && A->columnindex == B->columnindex && A->m == B->m &&
                        A->n == B->n && tm == tn;
     bool s2elem = false, b_is_a = false;

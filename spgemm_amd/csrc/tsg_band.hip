@@ -46,12 +46,11 @@ static_assert(BD_WORDS == 64, "one bitmap word per lane");
 }  // namespace
 
 // Per C row: its column window [lo, hi] (first / last column of the B rows its
-// entries reach; lo > hi for a row without products).  Statistics: bad[0] =
-// rows whose window is wider than BD_SPAN, bad[1] = the widest window,
-// bad[2..3] (u64) = the element products (they bound nnz(C)), bad[4..5] (u64)
-// = the windows' columns in all.
+// entries reach; lo > hi for a row without products).  Statistics (BandStats):
+// the rows whose window is wider than BD_SPAN, the widest window, the element
+// products (they bound nnz(C)) and the windows' columns in all.
 __global__ __launch_bounds__(WG) void k_band_stats(const int *rpA, const int *ciA, int m, const int *rpB,
-                                                   const int *ciB, int2 *win, long long *width, int *bad,
+                                                   const int *ciB, int2 *win, long long *width, BandStats *bad,
                                                    int2 *ebnd) {
     // 16 lanes per row, lane sl taking the row's entries sl, sl + 16, ... (four
     // entries' loads in flight): a row's ~64 entries (cant) are four dependent
@@ -118,18 +117,18 @@ __global__ __launch_bounds__(WG) void k_band_stats(const int *rpA, const int *ci
     const long long tp = block_sum(prod, red64);
     const long long tw = block_sum(wsum, red64);
     if (threadIdx.x == 0) {  // (spread over BD_SLOTS copies: thousands of workgroups, no one hot address)
-        int *const b = bad + 6 * (blockIdx.x % BD_SLOTS);
-        if (tb) atomicAdd(&b[0], tb);
-        if (wmax) atomicMax(&b[1], wmax);
-        if (tp) atomicAdd(reinterpret_cast<unsigned long long *>(b + 2), (unsigned long long)tp);
-        if (tw) atomicAdd(reinterpret_cast<unsigned long long *>(b + 4), (unsigned long long)tw);
+        BandStats *const b = bad + blockIdx.x % BD_SLOTS;
+        if (tb) atomicAdd(&b->wide, tb);
+        if (wmax) atomicMax(&b->wmax, wmax);
+        if (tp) atomicAdd(&b->products, (unsigned long long)tp);
+        if (tw) atomicAdd(&b->wcols, (unsigned long long)tw);
     }
 }
 
 // the BD_SLOTS copies of the statistics into the first (the first wave); with
 // spart, also B's sortedness shares (up to 4,096) summed by the workgroup into
 // the host-mapped flag (the work of k_rows_sorted_final, in the same launch)
-__global__ __launch_bounds__(WG) void k_band_stats_final(int *bad, const int *spart, int snb, int *sflag) {
+__global__ __launch_bounds__(WG) void k_band_stats_final(BandStats *bad, const int *spart, int snb, int *sflag) {
     __shared__ long long red[WAVES];
     const int l = threadIdx.x;
     if (spart) {  // (workgroup-uniform)
@@ -140,18 +139,15 @@ __global__ __launch_bounds__(WG) void k_band_stats_final(int *bad, const int *sp
         if (l == 0 && v != 0) __hip_atomic_store(sflag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     if (l >= 64) return;
-    int nb = l < BD_SLOTS ? bad[6 * l] : 0, wm = l < BD_SLOTS ? bad[6 * l + 1] : 0;
-    long long tp = l < BD_SLOTS ? *reinterpret_cast<const long long *>(bad + 6 * l + 2) : 0;
-    long long tw = l < BD_SLOTS ? *reinterpret_cast<const long long *>(bad + 6 * l + 4) : 0;
+    int nb = l < BD_SLOTS ? bad[l].wide : 0, wm = l < BD_SLOTS ? bad[l].wmax : 0;
+    long long tp = l < BD_SLOTS ? (long long)bad[l].products : 0;
+    long long tw = l < BD_SLOTS ? (long long)bad[l].wcols : 0;
     nb = wave_sum(nb);
     wm = wave_last(wave_incl_max(wm));
     tp = wave_sum(tp);
     tw = wave_sum(tw);
     if (l == 0) {  // (one wave: its reads of every slot are done, the sums need them)
-        bad[0] = nb;
-        bad[1] = wm;
-        *reinterpret_cast<long long *>(bad + 2) = tp;
-        *reinterpret_cast<long long *>(bad + 4) = tw;
+        *bad = BandStats{nb, wm, (unsigned long long)tp, (unsigned long long)tw};
     }
 }
 
@@ -353,34 +349,27 @@ int dev_band_check(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, bool
     PoolScope ws(cx);
     int2 *win = nullptr, *ebnd = nullptr;
     long long *width = nullptr;
-    int *bad = nullptr;
+    BandStats *bad = nullptr;
     TSG_TRY(ws.get(&win, (size_t)A.m));
     TSG_TRY(ws.get(&width, (size_t)A.m + 1));
     TSG_TRY(ws.get(&ebnd, (size_t)A.nnz + 1));
-    TSG_TRY(ws.get(&bad, 6 * BD_SLOTS));
-    TSG_HIP(hipMemsetAsync(bad, 0, 6 * BD_SLOTS * sizeof(int), s));
+    TSG_TRY(ws.get(&bad, BD_SLOTS));
+    TSG_HIP(hipMemsetAsync(bad, 0, BD_SLOTS * sizeof(BandStats), s));
     k_band_stats<<<grid_for(A.m, WG / 16, 16384), WG, 0, s>>>(A.rowpointer, A.columnindex, A.m, B.rowpointer,
                                                         B.columnindex, win, width, bad, ebnd);
     const bool shares = sh && sh->part;
     k_band_stats_final<<<1, WG, 0, s>>>(bad, shares ? sh->part : nullptr, shares ? sh->nb : 0,
                                          shares ? sh->dflag : nullptr);
     TSG_HIP(hipGetLastError());
-    TSG_HIP(hipMemcpyAsync(cx.pinned + 8, bad, 6 * sizeof(int), hipMemcpyDeviceToHost, s));
+    const BandStats &h = cx.slots->band;
+    TSG_HIP(hipMemcpyAsync(&cx.slots->band, bad, sizeof(BandStats), hipMemcpyDeviceToHost, s));
     TSG_TRY(stream_wait(s));
-    const long long products = *reinterpret_cast<const long long *>(cx.pinned + 10);
-    const long long wcols = *reinterpret_cast<const long long *>(cx.pinned + 12);
-    if (cx.pinned[8] == 0 && (force || products >= wcols)) {
+    const long long products = (long long)h.products, wcols = (long long)h.wcols;
+    if (h.wide == 0 && (force || products >= wcols)) {
         *ok = true;
         *bw = BandWin{ws.keep(win), ws.keep(width), products, wcols, ws.keep(ebnd)};
     }
     return TSG_OK;
-}
-
-__global__ __launch_bounds__(WG) void k_band_ebnd(const int *ciA, long nnzA, const int *rpB, int2 *ebnd) {
-    for (long a = (long)blockIdx.x * WG + threadIdx.x; a < nnzA; a += (long)gridDim.x * WG) {
-        const int k = ciA[a];
-        ebnd[a] = make_int2(rpB[k], rpB[k + 1]);
-    }
 }
 
 // CSR in -> CSR out for a banded product (windows from dev_band_check, the
@@ -399,8 +388,7 @@ int dev_spgemm_band(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, con
     double *Sval = nullptr;
     if (!ebnd) {
         TSG_TRY(ws.get(&ebnd, (size_t)A.nnz + 1));
-        if (A.nnz > 0) k_band_ebnd<<<grid_for(A.nnz, WG, 16384), WG, 0, s>>>(A.columnindex, A.nnz, B.rowpointer, ebnd);
-        TSG_HIP(hipGetLastError());
+        TSG_TRY(launch_entry_bounds(A, B, ebnd, s));
     }
     // staging: BD_SPAN slots per row while that stays within 2 GiB and within 4x
     // the window columns (no scan of the window widths: two launches fewer; cant:
@@ -411,9 +399,7 @@ int dev_spgemm_band(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, con
     TSG_TRY(ws.get(&Sval, (size_t)slots + 1));
     TSG_TRY(ws.get(&C.rowpointer, (size_t)m + 1));
     if (!fixed) {  // window widths -> staging offsets
-        const int rc = dev_scan_i64_fused(cx, bw.width, (long)m + 1, s);
-        if (rc == TSG_ERR_UNSUPPORTED) TSG_TRY(scan_exclusive_i64(cx, bw.width, (long)m + 1, s));
-        else TSG_TRY(rc);
+        TSG_TRY(dev_scan_i64(cx, bw.width, (long)m + 1, s));
     }
     const long long *soff = fixed ? nullptr : bw.width;
     if (ev && cx.stage_ev) TSG_HIP(hipEventRecord(ev[1], s));
@@ -431,13 +417,10 @@ int dev_spgemm_band(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, con
     // checked scan reads it back first and C is sized exactly.
     long long nnz = 0;
     if (m == 0) TSG_HIP(hipMemsetAsync(C.rowpointer + m, 0, sizeof(int), s));  // (else k_band_rows writes it)
-    bool fused = bw.wcols <= 0x7fffffffLL && bw.wcols * 12 <= kRowsProductSizedC;
-    int *const hnnz = reinterpret_cast<int *>(cx.pinned64 + 15);
-    if (fused) {
-        const int rc = dev_scan_rows_fused(cx, C.rowpointer, m, reinterpret_cast<int *>(cx.dpinned64 + 15), s);
-        if (rc == TSG_ERR_UNSUPPORTED) fused = false;
-        else TSG_TRY(rc);
-    }
+    // (more rows than the fused scan takes: the checked scan as well)
+    const bool fused = bw.wcols <= 0x7fffffffLL && bw.wcols * 12 <= kRowsProductSizedC && scan_fuses((long)m + 1);
+    const int *const hnnz = &cx.slots->nnz_c;
+    if (fused) TSG_TRY(dev_scan_rows(cx, C.rowpointer, m, nullptr, &cx.dslots->nnz_c, s));
     if (fused && (ws.get(&C.columnindex, (size_t)bw.wcols + 1) != TSG_OK ||
                   ws.get(&C.value, (size_t)bw.wcols + 1) != TSG_OK)) {
         (void)hipGetLastError();

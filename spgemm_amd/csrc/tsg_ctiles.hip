@@ -247,7 +247,7 @@ namespace tsg {
 // C (16 x 16, step 1's tile structure: tile_ptr, tile_columnidx, numtile) gets
 // tile_nnz, tile_csr_Ptr, mask, tile_csr_Col and tile_csr_Value from the CSR C
 // Cc (rows column-sorted, every nonzero inside some C tile).  Queued only; an
-// entry outside the structure (never expected) sets cx.pinned[8] at the
+// entry outside the structure (never expected) sets cx.slots->ctiles_fail at the
 // caller's next synchronisation.
 int dev_ctiles_from_csr(Context &cx, const tsg_dev_csr &Cc, tsg_dev_tiles &C, hipStream_t s) {
     if (C.tile_m != 16 || C.tile_n != 16 || Cc.m != C.m) return TSG_ERR_INVALID;
@@ -267,8 +267,8 @@ int dev_ctiles_from_csr(Context &cx, const tsg_dev_csr &Cc, tsg_dev_tiles &C, hi
     TSG_TRY(ws.get(&units, (size_t)umax));
     TSG_TRY(ws.get(&ulo, 16 * (size_t)umax + 16));
     TSG_HIP(hipMemsetAsync(fail, 0, 2 * sizeof(int), s));
-    cx.pinned[9] = Cc.nnz;  // tile_nnz[numtile] = nnz(C)
-    TSG_HIP(hipMemcpyAsync(C.tile_nnz + C.numtile, cx.pinned + 9, sizeof(int), hipMemcpyHostToDevice, s));
+    cx.slots->ctiles_nnz = Cc.nnz;  // tile_nnz[numtile] = nnz(C)
+    TSG_HIP(hipMemcpyAsync(C.tile_nnz + C.numtile, &cx.slots->ctiles_nnz, sizeof(int), hipMemcpyHostToDevice, s));
     if (C.tilem > 0 && C.numtile > 0) {
         k_ct_count<<<grid_for(C.tilem, WG, 4096), WG, 0, s>>>(C.tile_ptr, C.tilem, ubase);
         TSG_HIP(hipMemsetAsync(ubase + C.tilem, 0, sizeof(int), s));
@@ -283,8 +283,8 @@ int dev_ctiles_from_csr(Context &cx, const tsg_dev_csr &Cc, tsg_dev_tiles &C, hi
     else if (Cc.nnz > 0)
         TSG_HIP(hipMemsetAsync(fail, 1, 1, s));  // (nonzeros but no tiles to hold them)
     TSG_HIP(hipGetLastError());
-    cx.pinned[8] = 0;
-    TSG_HIP(hipMemcpyAsync(cx.pinned + 8, fail, sizeof(int), hipMemcpyDeviceToHost, s));
+    cx.slots->ctiles_fail = 0;
+    TSG_HIP(hipMemcpyAsync(&cx.slots->ctiles_fail, fail, sizeof(int), hipMemcpyDeviceToHost, s));
     keep_blocks(ws, C);
     return TSG_OK;  // (the temporaries return here; stream-ordered reuse: the copies above precede any later use)
 }

@@ -1,6 +1,7 @@
 // tsg_dev_common.h -- wave64 / workgroup primitives shared by the gfx950 kernels
-// (tsg_device.hip: csr2tile, the tiled steps, tile2csr; tsg_rows.hip, tsg_band.hip:
-// the row-merge and banded CSR paths).  Device code only; include after tsg_internal.h.
+// (tsg_device.hip: the scans, csr2tile, the tiled steps, tile2csr; tsg_tile_steps.hip,
+// tsg_ctiles.hip: the reference tiled layout; tsg_rows.hip, tsg_band.hip: the CSR paths;
+// tsg_numeric.hip, tsg_masked.hip: the plans).  Device code only; include after tsg_internal.h.
 #pragma once
 
 #include <climits>
@@ -15,6 +16,19 @@ typedef unsigned short u16;
 
 constexpr int WG = 256;
 constexpr int WAVES = WG / 64;
+
+// the device-wide scans' tile (tsg_device.hip): values per workgroup.  Up to
+// RS_INLINE_MAX tiles a scan takes the two-launch fused form (tile sums, then
+// an apply that adds up the earlier tiles' sums itself), past it the generic
+// three stages.
+constexpr int SCAN_ITEMS = 16;
+constexpr int SCAN_TILE = WG * SCAN_ITEMS;  // 4096
+constexpr int RS_INLINE_MAX = 2048;
+static inline long scan_tiles(long n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
+static inline bool scan_fuses(long n) { return scan_tiles(n) <= RS_INLINE_MAX; }
+// positions per chunk of the row-merge compaction (k_rows_compact; the fused
+// row-pointer scan fills its chunk table)
+constexpr int CP_CH = 2048;
 
 // ---------------------------------------------------------------------------
 // wave / workgroup primitives
@@ -164,6 +178,22 @@ __device__ __forceinline__ int owner_search(const int *off, int n, int it) {
         if (off[mid] <= it) lo = mid; else hi = mid - 1;
     }
     return lo;
+}
+
+// rank of column c inside an LDS bitmap window: blk[w / BLK] (int prefix per
+// block of BLK words) + g4[w / 4] (u16 prefix per 4-word group inside its
+// block) + the bits of the group's earlier words + the bits below c in its word
+template <int BLK>
+__device__ __forceinline__ int bitmap_rank(const u64 *bm, const u16 *g4, const int *blk, int c) {
+    const int w = c >> 6, gi = w >> 2, sub = w & 3;
+    const ulonglong2 lo = reinterpret_cast<const ulonglong2 *>(bm)[gi * 2];
+    const ulonglong2 hi = reinterpret_cast<const ulonglong2 *>(bm)[gi * 2 + 1];
+    const u64 word = sub == 0 ? lo.x : sub == 1 ? lo.y : sub == 2 ? hi.x : hi.y;
+    int rk = blk[w / BLK] + g4[gi] + __popcll(word & ((1ull << (c & 63)) - 1ull));
+    rk += sub > 0 ? __popcll(lo.x) : 0;
+    rk += sub > 1 ? __popcll(lo.y) : 0;
+    rk += sub > 2 ? __popcll(hi.x) : 0;
+    return rk;
 }
 
 // XCD-aware work order: the dispatcher deals a grid's workgroups round-robin

@@ -35,61 +35,114 @@ static int ablate_bits() {
 }
 
 // ---------------------------------------------------------------------------
-// device-wide exclusive scan (reduce -> scan partials -> apply), in place
+// device-wide exclusive scans, in place, over tiles of SCAN_TILE values.
+//   generic: tile sums -> their scan -> apply (each tile reads its scanned sum)
+//   fused:   tile sums -> apply (each tile adds up the earlier tiles' sums
+//            itself): two launches, for up to RS_INLINE_MAX tiles -- at
+//            mc2depi's size every launch costs 4-5 us however little it does
 // ---------------------------------------------------------------------------
-constexpr int SCAN_ITEMS = 16;
-constexpr int SCAN_TILE = WG * SCAN_ITEMS;  // 4096 elements per block
 __device__ __forceinline__ int scan_pad(int i) { return i + (i >> 4); }
 
-template <class T> __global__ __launch_bounds__(WG) void k_scan_reduce(const T *a, long n, T *part) {
-    __shared__ T red[WAVES];
-    long base = (long)blockIdx.x * SCAN_TILE;
-    T s = 0;
+// per tile its sum (P wider than T: int counts summed in int64).  N1: also
+// part[tiles] = 0, the "n+1 scan" slot of the partials.
+template <class T, class P = T, bool N1 = false>
+__global__ __launch_bounds__(WG) void k_scan_reduce(const T *a, long n, P *part) {
+    __shared__ P red[WAVES];
+    const long base = (long)blockIdx.x * SCAN_TILE;
+    P s = 0;
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) {
-        long i = base + k * WG + threadIdx.x;
+        const long i = base + k * WG + threadIdx.x;
         if (i < n) s += a[i];
     }
-    T tot = block_sum(s, red);
+    const P tot = block_sum(s, red);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
+    if (N1 && blockIdx.x == 0 && threadIdx.x == 0) part[gridDim.x] = 0;
 }
 
-template <class T, class P = T>
-__global__ __launch_bounds__(WG) void k_scan_apply(T *a, long n, const P *part) {
-    __shared__ T tile[SCAN_TILE + SCAN_TILE / 16];
-    __shared__ T red[WAVES];
-    long base = (long)blockIdx.x * SCAN_TILE;
+// One tile of the scan: the tile into padded LDS, a serial pass per thread,
+// the workgroup's scan on top of the tile's prefix, and back.  prefix(red) is
+// called between the tile's LDS stores and their first read, so it holds a
+// workgroup barrier; each(i, off, v) sees every value v at i of the tile with
+// its scanned offset.
+template <class T, class Pre, class Each>
+__device__ __forceinline__ void scan_tile(T *a, long n, T *tile, T *red, Pre &&prefix, Each &&each) {
+    const int tid = threadIdx.x;
+    const long base = (long)blockIdx.x * SCAN_TILE;
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) {
-        int li = k * WG + threadIdx.x;
-        long i = base + li;
+        const int li = k * WG + tid;
+        const long i = base + li;
         tile[scan_pad(li)] = (i < n) ? a[i] : T(0);
     }
-    __syncthreads();
+    const T pre = prefix(red);
     T s = 0;
 #pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) s += tile[scan_pad(threadIdx.x * SCAN_ITEMS + k)];
+    for (int k = 0; k < SCAN_ITEMS; ++k) s += tile[scan_pad(tid * SCAN_ITEMS + k)];
     T tot;
-    T off = block_excl_scan(s, &tot, red) + (part ? (T)part[blockIdx.x] : T(0));
+    T off = block_excl_scan(s, &tot, red) + pre;
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) {
-        int li = scan_pad(threadIdx.x * SCAN_ITEMS + k);
-        T v = tile[li];
+        const int li = scan_pad(tid * SCAN_ITEMS + k);
+        const T v = tile[li];
         tile[li] = off;
+        each(tid * SCAN_ITEMS + k, off, v);
         off += v;
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < SCAN_ITEMS; ++k) {
-        int li = k * WG + threadIdx.x;
-        long i = base + li;
+        const int li = k * WG + tid;
+        const long i = base + li;
         if (i < n) a[i] = tile[scan_pad(li)];
     }
 }
 
+// the generic apply: the tile's prefix is its scanned sum (null: one tile)
+template <class T, class P = T>
+__global__ __launch_bounds__(WG) void k_scan_apply(T *a, long n, const P *part) {
+    __shared__ T tile[SCAN_TILE + SCAN_TILE / 16];
+    __shared__ T red[WAVES];
+    scan_tile(
+        a, n, tile, red,
+        [&](T *) {
+            __syncthreads();
+            return part ? (T)part[blockIdx.x] : T(0);
+        },
+        [](int, T, T) {});
+}
+
+// the fused apply: the tile's prefix summed from the earlier tiles' sums.
+// CFIRST (the row pointers, n = m + 1): also the row-merge compaction's chunk
+// table (k_rows_cfirst's job: the row holding each chunk's first position) and
+// nnz(C) (the scan's last value) into the caller's host-mapped *hnnz.
+template <class T, bool CFIRST>
+__global__ __launch_bounds__(WG) void k_scan_apply_fused(T *a, long n, const T *part, int *cfirst, int m,
+                                                         int *hnnz) {
+    __shared__ T tile[SCAN_TILE + SCAN_TILE / 16];
+    __shared__ T red[WAVES];
+    const long base = (long)blockIdx.x * SCAN_TILE;
+    T pre = 0;  // (these loads ahead of the tile's)
+    for (int i = threadIdx.x; i < (int)blockIdx.x; i += WG) pre += part[i];
+    scan_tile(
+        a, n, tile, red, [&](T *r) { return block_sum(pre, r); },  // (its barriers also publish the tile)
+        [&](int i, T off, T v) {
+            if constexpr (CFIRST) {
+                const long r = base + i;
+                if (r < m) {
+                    if (cfirst)
+                        for (long long b = ((long long)off + CP_CH - 1) / CP_CH; b * CP_CH < (long long)off + v; ++b)
+                            cfirst[b] = (int)r;
+                } else if (r == m && hnnz) {
+                    __hip_atomic_store(hnnz, (int)off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
+            }
+        });
+}
+
 template <class T> static int scan_exclusive(Context &cx, T *a, long n, hipStream_t s) {
     if (n <= 0) return TSG_OK;
-    long nb = (n + SCAN_TILE - 1) / SCAN_TILE;
+    const long nb = scan_tiles(n);
     if (nb == 1) {
         k_scan_apply<T><<<1, WG, 0, s>>>(a, n, (const T *)nullptr);
         TSG_HIP(hipGetLastError());
@@ -111,29 +164,47 @@ template <class T> static int scan_exclusive(Context &cx, T *a, long n, hipStrea
 }
 
 int scan_exclusive_i32(Context &cx, int *a, long n, hipStream_t s) { return scan_exclusive(cx, a, n, s); }
+int scan_exclusive_i64(Context &cx, long long *a, long n, hipStream_t s) { return scan_exclusive(cx, a, n, s); }
 
-__global__ __launch_bounds__(WG) void k_scan_reduce_wide(const int *a, long n, long long *part) {
-    __shared__ long long red[WAVES];
-    const long base = (long)blockIdx.x * SCAN_TILE;
-    long long s = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) {
-        const long i = base + k * WG + threadIdx.x;
-        if (i < n) s += a[i];
-    }
-    const long long tot = block_sum(s, red);
-    if (threadIdx.x == 0) part[blockIdx.x] = tot;
-    if (blockIdx.x == 0 && threadIdx.x == 0) part[gridDim.x] = 0;  // the "n+1 scan" slot of the partials
+// the fused form: tile sums, then the apply (part returns to the pool when the
+// scope ends: stream-ordered reuse)
+template <class T, bool CFIRST>
+static int scan_fused(Context &cx, T *a, long n, int *cfirst, int m, int *hnnz, hipStream_t s) {
+    const long nt = scan_tiles(n);
+    PoolScope ws(cx);
+    T *part = nullptr;
+    TSG_TRY(ws.get(&part, (size_t)nt));
+    k_scan_reduce<T><<<(unsigned)nt, WG, 0, s>>>(a, n, part);
+    k_scan_apply_fused<T, CFIRST><<<(unsigned)nt, WG, 0, s>>>(a, n, part, cfirst, m, hnnz);
+    TSG_HIP(hipGetLastError());
+    return TSG_OK;
 }
 
-// int32 exclusive scan whose block partials run in int64: *total = the exact
-// sum (read back synchronously); TSG_ERR_OVERFLOW, with `a` left unscanned,
-// when it does not fit an int32 index (C tile counts, nnz(C)).
-// Exclusive int32 scan whose int64 total is read back to the host.  The apply
-// kernel is queued before the read (the host round trip overlaps it); a total
-// past INT_MAX returns TSG_ERR_OVERFLOW (the scanned values are then invalid).
-// `before_read` (optional) queues more work ahead of the read, and extra_d
-// (optional) is read back into *extra_h by the same host synchronisation.
+int scan_apply_fused_i64(long long *a, long n, const long long *part, hipStream_t s) {
+    k_scan_apply_fused<long long, false><<<(unsigned)scan_tiles(n), WG, 0, s>>>(a, n, part, nullptr, 0, nullptr);
+    TSG_HIP(hipGetLastError());
+    return TSG_OK;
+}
+
+int dev_scan_i64(Context &cx, long long *a, long n, hipStream_t s) {
+    if (n <= 0) return TSG_OK;
+    return scan_fuses(n) ? scan_fused<long long, false>(cx, a, n, nullptr, 0, nullptr, s)
+                         : scan_exclusive(cx, a, n, s);
+}
+
+int dev_scan_rows(Context &cx, int *rp, int m, int *cfirst, int *hnnz_dev, hipStream_t s, bool *fused) {
+    const long n = (long)m + 1;
+    const bool f = scan_fuses(n);
+    if (fused) *fused = f;
+    return f ? scan_fused<int, true>(cx, rp, n, cfirst, m, hnnz_dev, s) : scan_exclusive(cx, rp, n, s);
+}
+
+// Exclusive int32 scan whose block partials run in int64 and whose exact int64
+// total is read back to the host.  The apply kernel is queued before the read
+// (the host round trip overlaps it); a total that does not fit an int32 index
+// (C tile counts, nnz(C)) returns TSG_ERR_OVERFLOW (the scanned values are then
+// invalid).  `before_read` (optional) queues more work ahead of the read, and
+// extra_d (optional) is read back into *extra_h by the same host synchronisation.
 template <class Fn>
 static int scan_i32_total_impl(Context &cx, int *a, long n, hipStream_t s, long long *total, Fn &&before_read,
                                const long long *extra_d, long long *extra_h) {
@@ -142,27 +213,25 @@ static int scan_i32_total_impl(Context &cx, int *a, long n, hipStream_t s, long 
     long long *part = nullptr;
     long nb = 0;
     if (n > 0) {
-        nb = (n + SCAN_TILE - 1) / SCAN_TILE;
+        nb = scan_tiles(n);
         TSG_TRY(ws.get(&part, (size_t)nb + 1));
-        k_scan_reduce_wide<<<(unsigned)nb, WG, 0, s>>>(a, n, part);
+        k_scan_reduce<int, long long, true><<<(unsigned)nb, WG, 0, s>>>(a, n, part);
         TSG_HIP(hipGetLastError());
         TSG_TRY(scan_exclusive(cx, part, nb + 1, s));
         k_scan_apply<int, long long><<<(unsigned)nb, WG, 0, s>>>(a, n, part);
         TSG_HIP(hipGetLastError());
     }
     before_read();
-    if (part) TSG_HIP(hipMemcpyAsync(cx.pinned64, part + nb, sizeof(long long), hipMemcpyDeviceToHost, s));
-    if (extra_d) TSG_HIP(hipMemcpyAsync(cx.pinned64 + 1, extra_d, sizeof(long long), hipMemcpyDeviceToHost, s));
+    HostSlots &h = *cx.slots;
+    if (part) TSG_HIP(hipMemcpyAsync(&h.scan_total, part + nb, sizeof(long long), hipMemcpyDeviceToHost, s));
+    if (extra_d) TSG_HIP(hipMemcpyAsync(&h.scan_extra, extra_d, sizeof(long long), hipMemcpyDeviceToHost, s));
     if (part || extra_d) TSG_TRY(stream_wait(s));
-    if (part) *total = cx.pinned64[0];
-    if (extra_d) *extra_h = cx.pinned64[1];
+    if (part) *total = h.scan_total;
+    if (extra_d) *extra_h = h.scan_extra;
     return *total > 0x7fffffffll ? TSG_ERR_OVERFLOW : TSG_OK;
 }
 int scan_exclusive_i32_total(Context &cx, int *a, long n, hipStream_t s, long long *total) {
     return scan_i32_total_impl(cx, a, n, s, total, [] {}, nullptr, nullptr);
-}
-int scan_exclusive_i64(Context &cx, long long *a, long n, hipStream_t s) {
-    return scan_exclusive(cx, a, n, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -391,16 +460,16 @@ int launch_nnzcub(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, u64 *
 }
 
 int read_i32(Context &cx, const int *d, int *h, hipStream_t s) {
-    TSG_HIP(hipMemcpyAsync(cx.pinned, d, sizeof(int), hipMemcpyDeviceToHost, s));
+    TSG_HIP(hipMemcpyAsync(&cx.slots->i32, d, sizeof(int), hipMemcpyDeviceToHost, s));
     TSG_TRY(stream_wait(s));
-    *h = cx.pinned[0];
+    *h = cx.slots->i32;
     return TSG_OK;
 }
 
 int read_i64(Context &cx, const long long *d, long long *h, hipStream_t s) {
-    TSG_HIP(hipMemcpyAsync(cx.pinned64, d, sizeof(long long), hipMemcpyDeviceToHost, s));
+    TSG_HIP(hipMemcpyAsync(&cx.slots->i64, d, sizeof(long long), hipMemcpyDeviceToHost, s));
     TSG_TRY(stream_wait(s));
-    *h = cx.pinned64[0];
+    *h = cx.slots->i64;
     return TSG_OK;
 }
 
@@ -1340,6 +1409,11 @@ __global__ __launch_bounds__(WG) void k_entry_bounds(const int *ciA, long nnzA, 
         ebnd[p] = make_int2(rpB[k], rpB[k + 1]);
     }
 }
+int launch_entry_bounds(const tsg_dev_csr &A, const tsg_dev_csr &B, int2 *ebnd, hipStream_t s) {
+    if (A.nnz > 0) k_entry_bounds<<<grid_for(A.nnz, WG, 16384), WG, 0, s>>>(A.columnindex, A.nnz, B.rowpointer, ebnd);
+    TSG_HIP(hipGetLastError());
+    return TSG_OK;
+}
 
 // Row sortedness with no search: D = the non-ascents ci[p] <= ci[p-1] over
 // all entries (a descent, or a column repeated), R = those at the first entry
@@ -1521,9 +1595,9 @@ int dev_rows_sorted_async(Context &cx, const tsg_dev_csr &M, int *host_flag, hip
     return dev_rows_sorted_finish(cx, sh, s);  // (the shares return here: stream-ordered reuse)
 }
 int dev_rows_sorted(Context &cx, const tsg_dev_csr &M, bool *sorted, hipStream_t s) {
-    TSG_TRY(dev_rows_sorted_async(cx, M, cx.pinned + 1, s));
+    TSG_TRY(dev_rows_sorted_async(cx, M, &cx.slots->b_unsorted, s));
     TSG_TRY(stream_wait(s));
-    *sorted = cx.pinned[1] == 0;
+    *sorted = cx.slots->b_unsorted == 0;
     return TSG_OK;
 }
 
@@ -2498,8 +2572,7 @@ int dev_step1(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, tsg_d
     long long *ubuf_off = nullptr;
     long long slots = 0;
     if (fill_ebnd && !capk) {  // no capacity kernel to fuse into
-        k_entry_bounds<<<grid_for(Ael->nnz, WG, 16384), WG, 0, s>>>(Ael->columnindex, Ael->nnz, Bel->rowpointer,
-                                                                   ebnd);
+        TSG_TRY(launch_entry_bounds(*Ael, *Bel, ebnd, s));
         fill_ebnd = false;
     }
     if (capk) {
@@ -2621,9 +2694,7 @@ int dev_tilespgemm(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, 
     if ((s2elem || s3elem) && Acsr->nnz > 0) {
         TSG_TRY(ws.get(&ebnd, (size_t)Acsr->nnz + 1));
         if (!s1elem) {  // (element step 1 fills them in its capacity kernel)
-            k_entry_bounds<<<grid_for(Acsr->nnz, WG, 16384), WG, 0, s>>>(Acsr->columnindex, Acsr->nnz,
-                                                                        Bcsr->rowpointer, ebnd);
-            TSG_HIP(hipGetLastError());
+            TSG_TRY(launch_entry_bounds(*Acsr, *Bcsr, ebnd, s));
         }
     }
     // CSR path: C tiles indexed in step 1's unit-buffer space when it allows (no
@@ -2667,11 +2738,12 @@ int dev_tilespgemm(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, 
     }
     int nunits = 0;
     long long ne = 0;
-    TSG_HIP(hipMemcpyAsync(cx.pinned, uoff + tilemA, sizeof(int), hipMemcpyDeviceToHost, s));
-    if (ebase) TSG_HIP(hipMemcpyAsync(cx.pinned64, ebase + tilemA, sizeof(long long), hipMemcpyDeviceToHost, s));
+    HostSlots &hs = *cx.slots;
+    TSG_HIP(hipMemcpyAsync(&hs.tile_units, uoff + tilemA, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (ebase) TSG_HIP(hipMemcpyAsync(&hs.tile_entries, ebase + tilemA, sizeof(long long), hipMemcpyDeviceToHost, s));
     TSG_TRY(stream_wait(s));
-    nunits = cx.pinned[0];
-    if (ebase) ne = cx.pinned64[0];
+    nunits = hs.tile_units;
+    if (ebase) ne = hs.tile_entries;
     const int gu = grid_for(maxu, 1, TSG_GU_CAP);  // workgroups of steps 2 and 3 (units strided over them)
     // tile-product split points: every A tile's B tile row cut at its C tile row's unit boundaries
     long long *sbase = nullptr;
@@ -2810,9 +2882,9 @@ int dev_tilespgemm(Context &cx, const tsg_dev_tiles &A, const tsg_dev_tiles &B, 
     }
     if (ev) TSG_HIP(hipEventRecord(ev[3], s));
     if (defer_nnz) {  // the pipeline's one read-back after step 3
-        TSG_HIP(hipMemcpyAsync(cx.pinned, csr_out->rowpointer + A.m, sizeof(int), hipMemcpyDeviceToHost, s));
+        TSG_HIP(hipMemcpyAsync(&hs.tile_nnz_c, csr_out->rowpointer + A.m, sizeof(int), hipMemcpyDeviceToHost, s));
         TSG_TRY(stream_wait(s));
-        nnzC = cx.pinned[0];
+        nnzC = hs.tile_nnz_c;
         C.nnz = nnzC;
         csr_out->nnz = nnzC;
     }

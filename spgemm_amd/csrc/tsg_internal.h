@@ -1,5 +1,6 @@
-// tsg_internal.h -- host-side internals shared by the device code (tsg_device.hip)
-// and the C-ABI layer (tsg_api.cpp).  gfx950 / wave64 only.
+// tsg_internal.h -- host-side internals shared by the device code (the .hip
+// files: each declaration below names the one that implements it, tsg_device.hip
+// where none is named) and the C-ABI layer (tsg_api.cpp).  gfx950 / wave64 only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -69,13 +70,86 @@ struct Knobs {
     bool dr_per_row = false;         // TSG_DR_PER_ROW (tests): per-row chunks also below DR_GMAX rows
 };
 
+// The row-merge setup's device counters (RowsPlan::cls).  The entry kernels zero
+// the block as 32 ints and the setup reads it back up to kReadBytes in one copy,
+// so the layout is part of the kernels' contract.
+struct RowsCounters {
+    int ncls[8];                    // rows per class
+    unsigned long long hprod;       // class-H rows' products
+    unsigned long long pmax;        // the longest row's products
+    unsigned long long products;    // all products
+    unsigned long long hubprod;     // hub rows' products (past kRowsHubProducts)
+    unsigned long long hk;          // class-H rows with more runs than the one-walk kernel takes
+    int pad0[2];
+    int dr_chunks, dr_rows;         // the dominant-run kernels' cursors: fill chunks, rows
+    int pad1[2];
+    unsigned long long hbig;        // class-H rows' products past the one-walk register share
+    unsigned long long ow_cursor;   // the one-walk kernel's scratch cursor
+    int pad2[4];
+    static constexpr size_t kReadBytes = 26 * sizeof(int);  // the host's part: everything before ow_cursor
+};
+static_assert(sizeof(RowsCounters) == 32 * sizeof(int), "the entry kernels zero 32 ints");
+static_assert(offsetof(RowsCounters, hprod) == 32 && offsetof(RowsCounters, dr_chunks) == 80 &&
+                  offsetof(RowsCounters, hbig) == 96 && offsetof(RowsCounters, ow_cursor) == RowsCounters::kReadBytes,
+              "RowsCounters: the layout the row-merge kernels were measured with");
+
+// the band check's statistics (tsg_band.hip: one record per slot on the device, their total read back)
+struct BandStats {
+    int wide;             // rows whose window is wider than the kernel's span
+    int wmax;             // the widest window
+    unsigned long long products;  // element products (they bound nnz(C))
+    unsigned long long wcols;     // window columns in all
+};
+static_assert(sizeof(BandStats) == 6 * sizeof(int), "BandStats: the check's copy and memset count six ints");
+
+// the hub plan's device counters (tsg_rows.hip, k_rows_wplan)
+struct HubCounters {
+    unsigned long long wprod;    // windowed rows' products
+    unsigned long long drprod;   // dominant-run rows' products
+    unsigned long long ndr;      // dominant-run rows
+    unsigned long long pad;
+};
+
+// The windowed fill lists' three sizes in one u64 (one atomic per wave instead
+// of three): 21 bits each, so fewer than kFillListMax units.
+constexpr int kFillListBits = 21, kFillListMax = 1 << kFillListBits;
+struct FillSizes { int sort, heavy, mid; };  // the sort fill's units, the bitmap fill's past / within a workgroup's registers
+__host__ __device__ inline unsigned long long fill_sizes_pack(int sort, int heavy, int mid) {
+    return (unsigned long long)sort | ((unsigned long long)heavy << kFillListBits) |
+           ((unsigned long long)mid << (2 * kFillListBits));
+}
+__host__ __device__ inline FillSizes fill_sizes_unpack(unsigned long long pk) {
+    return FillSizes{(int)(pk & (kFillListMax - 1)), (int)((pk >> kFillListBits) & (kFillListMax - 1)),
+                     (int)(pk >> (2 * kFillListBits))};
+}
+
+// Small results on their way to the host: one host-mapped block, one field per
+// use, so no two stages share a slot.  The fields come back by stream-ordered
+// copies, except those a kernel writes itself by a system-scope store.
+struct HostSlots {
+    int i32;                       // read_i32
+    long long i64;                 // read_i64
+    int b_unsorted;                // B's sortedness flag (written by kernels: dev_rows_sorted_*)
+    int nnz_c;                     // nnz(C) of the rows and band paths (written by the fused row-pointer scan)
+    long long scan_total, scan_extra;  // scan_exclusive_i32_total and the value read with it
+    int tile_units;                // the tile pipeline: step 2's units,
+    long long tile_entries;        //   its element split entries,
+    int tile_nnz_c;                //   nnz(C) of its CSR output
+    int ctiles_fail;               // dev_ctiles_from_csr: an entry outside the structure
+    int ctiles_nnz;                //   and nnz(C) on its way to the device
+    BandStats band;                // dev_band_check
+    RowsCounters rows;             // dev_rows_setup_async (its first kReadBytes)
+    HubCounters hub;               // rows_hub_plan: the counters,
+    int hub_units, hub_chunks;     //   the unit and chunk lists' sizes,
+    long long hub_nmat;            //   the chunk x window offset matrix's
+    unsigned long long fill_sizes; // the windowed fill lists' sizes (fill_sizes_pack)
+};
+
 struct Context {
     int device = 0;
     DevicePool pool;
-    int *pinned = nullptr;        // host pinned scratch for size read-backs
-    long long *pinned64 = nullptr;
-    int *dpinned = nullptr;        // device views of the pinned scratch (kernels report
-    long long *dpinned64 = nullptr; //   small results there by system-scope stores)
+    HostSlots *slots = nullptr;   // host pinned, for size read-backs
+    HostSlots *dslots = nullptr;  // its device view (kernels report small results there by system-scope stores)
     hipEvent_t ev[16];
     bool stage_ev = false;         // the stage events too (TSG_STAGE_EVENTS=1), not just the kernel bracket
     Knobs knobs;                   // the call's run-time knobs (read_knobs, tsg_api.cpp)
@@ -143,11 +217,27 @@ class PoolScope {
     int n_ = 0;
 };
 
-// ---- launchers implemented in tsg_device.hip (all stream-ordered, no sync) ----
+// ---- launchers (all stream-ordered, no sync; in tsg_device.hip unless a
+// comment names tsg_band, tsg_rows, tsg_ctiles, tsg_tile_steps, tsg_numeric or tsg_masked) ----
 // Exclusive scan in place over n elements (a[n-1] ends up = sum of a[0..n-2]
-// when the caller stored 0 there, i.e. the reference's "n+1 scan" idiom).
+// when the caller stored 0 there, i.e. the reference's "n+1 scan" idiom): the
+// generic three stages.
 int scan_exclusive_i32(Context &cx, int *a, long n, hipStream_t s);
 int scan_exclusive_i64(Context &cx, long long *a, long n, hipStream_t s);
+// exclusive scan (n+1 idiom) whose total is read back
+int scan_exclusive_i32_total(Context &cx, int *a, long n, hipStream_t s, long long *total);
+// The same scans in the two-launch fused form where scan_fuses(n)
+// (tsg_dev_common.h), else generic.  Row pointers (n = m + 1): the fused form
+// also stores nnz(C) into the host-mapped *hnnz_dev and fills cfirst (optional:
+// the row-merge compaction's chunk table); *fused (optional) reports whether it
+// ran -- the generic form does neither.
+int dev_scan_i64(Context &cx, long long *a, long n, hipStream_t s);
+int dev_scan_rows(Context &cx, int *rp, int m, int *cfirst, int *hnnz_dev, hipStream_t s, bool *fused = nullptr);
+// the fused form's second launch alone, for a caller whose own kernel produced
+// the tile sums (k_rows_entries_sum)
+int scan_apply_fused_i64(long long *a, long n, const long long *part, hipStream_t s);
+// per A entry its B row's [start, end) (nothing queued for an empty A)
+int launch_entry_bounds(const tsg_dev_csr &A, const tsg_dev_csr &B, int2 *ebnd, hipStream_t s);
 // Sort u64 keys ascending inside each segment [seg[i], seg[i+1]) in place.
 int segmented_sort_u64(Context &cx, unsigned long long *keys, const int *seg, int nseg,
                        long total, hipStream_t s);
@@ -229,7 +319,7 @@ struct RowsPlan {
     long long *E = nullptr;    // per A entry: prefix of the element products
     int4 *lists = nullptr;     // the classes' rows: (row, its first A entry, its A entries, -)
     long long *soff = nullptr; // per row: staging offset
-    int *cls = nullptr;        // class counts + statistics (device)
+    RowsCounters *cls = nullptr;  // class counts, statistics, cursors (device)
     int *rowpointer = nullptr; // C's row pointers (row counts until the scan)
     int ncls[8] = {};
     long long products = 0, hprod = 0, pmax = 0;  // all / class-H rows' products, the longest row's
@@ -281,13 +371,6 @@ template <class S> void put_blocks(PoolScope &ws, S &st) {  // returns them now 
 // ev (optional): 1 set up | 4..5 the row kernels | 3 end
 int dev_rows_run(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const RowsPlan &p, tsg_dev_csr &C,
                  tsg_stats *st, hipStream_t s, hipEvent_t *ev);
-// two-launch exclusive scans (tsg_rows.hip) for up to 2,048 tiles of 4,096
-// values (TSG_ERR_UNSUPPORTED past it): i64 in place; row pointers (n = m + 1)
-// with nnz(C) stored into the host-mapped *hnnz_dev by the kernel
-int dev_scan_i64_fused(Context &cx, long long *a, long n, hipStream_t s);
-int dev_scan_rows_fused(Context &cx, int *rp, int m, int *hnnz_dev, hipStream_t s);
-// exclusive scan (n+1 idiom) whose total is read back
-int scan_exclusive_i32_total(Context &cx, int *a, long n, hipStream_t s, long long *total);
 
 // numeric-only product on a known C pattern (tsg_numeric.hip, DESIGN.md section
 // 3.7).  Rows are classed at plan time by len_C (the row's pattern entries) and

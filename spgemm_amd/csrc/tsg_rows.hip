@@ -38,7 +38,6 @@ namespace {
 
 constexpr int S16_MAX = 16;           // class S16: products (and runs) per row, 4 rows per wave
 constexpr int RS_MAX = 64;            // class S64: products (and runs) per row, a wave
-constexpr int CP_CH = 2048;           // positions per chunk of the compaction (k_rows_compact)
 constexpr int S16_U = 2, S64_U = 2;   // rows per lane group of the S16 / S64 kernels (k_rows_small; S16 at
                                       // U = 4: 95 vs 86 us on mc2depi; U = 2: 4 us under U = 1)
 // merge classes M1..M4: products and runs per row, threads per row -- each
@@ -117,11 +116,17 @@ struct RowsArgs {
     double *Sval;
 };
 
+// the setup's counters zeroed by the first workgroup of its first kernel (no
+// separate memset in the stream): class counts, statistics, cursors
+__device__ __forceinline__ void rows_counters_reset(RowsCounters *cls) {
+    constexpr int N = sizeof(RowsCounters) / sizeof(int);
+    if (blockIdx.x == 0 && threadIdx.x < N) reinterpret_cast<int *>(cls)[threadIdx.x] = 0;
+}
+
 // per A entry: its B row's range and products (the latter scanned into E)
-// (also zeroes the binning kernel's counters: no separate memset in the stream)
 __global__ __launch_bounds__(WG) void k_rows_entries(const int *ciA, long nnzA, const int *rpB, int2 *ebnd,
-                                                     long long *E, int *cls) {
-    if (blockIdx.x == 0 && threadIdx.x < 32) cls[threadIdx.x] = 0;  // (class counts, statistics, cursors)
+                                                     long long *E, RowsCounters *cls) {
+    rows_counters_reset(cls);
     for (long a = (long)blockIdx.x * WG + threadIdx.x; a <= nnzA; a += (long)gridDim.x * WG) {
         if (a == nnzA) {
             E[a] = 0;
@@ -133,39 +138,32 @@ __global__ __launch_bounds__(WG) void k_rows_entries(const int *ciA, long nnzA, 
     }
 }
 
-// ---- the setup's and the row pointers' scans fused with their neighbours: at
-// mc2depi's size every launch costs 4-5 us however little it does, and the
-// generic scan is three (block sums, their scan, apply).  Up to RS_INLINE_MAX
-// tiles, each apply workgroup adds up the earlier tiles' sums itself.
-constexpr int RS_ITEMS = 16, RS_TILE = WG * RS_ITEMS;
-constexpr int RS_INLINE_MAX = 2048;
-__device__ __forceinline__ int rs_pad(int i) { return i + (i >> 4); }
-
-// the entry table with the first half of its scan: per A entry its B row's
-// range and products, per tile of RS_TILE entries their sum (E[nnzA] = 0: the
-// n+1 slot); also zeroes the binning kernel's counters
+// the entry table with the first half of its fused scan (the scan's tile sums
+// in the same launch; scan_apply_fused_i64 is the second half): per A entry its
+// B row's range and products, per tile of SCAN_TILE entries their sum
+// (E[nnzA] = 0: the n+1 slot)
 __global__ __launch_bounds__(WG) void k_rows_entries_sum(const int *ciA, long nnzA, const int *rpB, int2 *ebnd,
-                                                         long long *E, int *cls, long long *part) {
+                                                         long long *E, RowsCounters *cls, long long *part) {
     __shared__ long long red[WAVES];
     const int tid = threadIdx.x;
-    if (blockIdx.x == 0 && tid < 32) cls[tid] = 0;  // (class counts, statistics, cursors)
-    const long base = (long)blockIdx.x * RS_TILE;
-    int kk[RS_ITEMS];
+    rows_counters_reset(cls);
+    const long base = (long)blockIdx.x * SCAN_TILE;
+    int kk[SCAN_ITEMS];
 #pragma unroll
-    for (int u = 0; u < RS_ITEMS; ++u) {
+    for (int u = 0; u < SCAN_ITEMS; ++u) {
         const long a = base + u * WG + tid;
         kk[u] = a < nnzA ? ciA[a] : 0;
     }
-    int b0[RS_ITEMS], b1[RS_ITEMS];
+    int b0[SCAN_ITEMS], b1[SCAN_ITEMS];
 #pragma unroll
-    for (int u = 0; u < RS_ITEMS; ++u) {
+    for (int u = 0; u < SCAN_ITEMS; ++u) {
         const long a = base + u * WG + tid;
         b0[u] = a < nnzA ? rpB[kk[u]] : 0;
         b1[u] = a < nnzA ? rpB[kk[u] + 1] : 0;
     }
     long long sum = 0;
 #pragma unroll
-    for (int u = 0; u < RS_ITEMS; ++u) {
+    for (int u = 0; u < SCAN_ITEMS; ++u) {
         const long a = base + u * WG + tid;
         if (a < nnzA) {
             ebnd[a] = make_int2(b0[u], b1[u]);
@@ -177,71 +175,6 @@ __global__ __launch_bounds__(WG) void k_rows_entries_sum(const int *ciA, long nn
     }
     sum = block_sum(sum, red);
     if (tid == 0) part[blockIdx.x] = sum;
-}
-
-// per tile of RS_TILE values their sum
-template <class T>
-__global__ __launch_bounds__(WG) void k_rows_count_sum(const T *a, long n, T *part) {
-    __shared__ T red[WAVES];
-    const long base = (long)blockIdx.x * RS_TILE;
-    T sum = 0;
-#pragma unroll
-    for (int u = 0; u < RS_ITEMS; ++u) {
-        const long i = base + u * WG + threadIdx.x;
-        sum += i < n ? a[i] : 0;
-    }
-    sum = block_sum(sum, red);
-    if (threadIdx.x == 0) part[blockIdx.x] = sum;
-}
-
-// the exclusive scan's apply, the tile's prefix summed from the earlier tiles'
-// sums.  CFIRST (the row pointers, n = m + 1): also the compaction's chunk
-// table (k_rows_cfirst's job: the row holding each chunk's first position) and
-// nnz(C) (the scan's last value) into the caller's host-mapped *hnnz.
-template <class T, bool CFIRST>
-__global__ __launch_bounds__(WG) void k_rows_scan_apply(T *a, long n, const T *part, int *cfirst, int m, int *hnnz) {
-    __shared__ T tile[RS_TILE + RS_TILE / 16];
-    __shared__ T red[WAVES];
-    const int tid = threadIdx.x;
-    const long base = (long)blockIdx.x * RS_TILE;
-    T pre = 0;
-    for (int i = tid; i < (int)blockIdx.x; i += WG) pre += part[i];
-#pragma unroll
-    for (int u = 0; u < RS_ITEMS; ++u) {
-        const int li = u * WG + tid;
-        const long i = base + li;
-        tile[rs_pad(li)] = i < n ? a[i] : T(0);
-    }
-    pre = block_sum(pre, red);  // (its barriers also publish the tile)
-    T sum = 0;
-#pragma unroll
-    for (int u = 0; u < RS_ITEMS; ++u) sum += tile[rs_pad(tid * RS_ITEMS + u)];
-    T tot;
-    T off = block_excl_scan(sum, &tot, red) + pre;
-#pragma unroll
-    for (int u = 0; u < RS_ITEMS; ++u) {
-        const int li = rs_pad(tid * RS_ITEMS + u);
-        const T v = tile[li];
-        tile[li] = off;
-        if constexpr (CFIRST) {
-            const long r = base + tid * RS_ITEMS + u;
-            if (r < m) {
-                if (cfirst)
-                    for (long long b = ((long long)off + CP_CH - 1) / CP_CH; b * CP_CH < (long long)off + v; ++b)
-                        cfirst[b] = (int)r;
-            } else if (r == m && hnnz) {
-                __hip_atomic_store(hnnz, (int)off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-        off += v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < RS_ITEMS; ++u) {
-        const int li = u * WG + tid;
-        const long i = base + li;
-        if (i < n) a[i] = tile[rs_pad(li)];
-    }
 }
 
 __device__ __forceinline__ int row_class(long long P, int k) {
@@ -256,19 +189,15 @@ __device__ __forceinline__ int row_class(long long P, int k) {
     return 7;
 }
 
-// rows -> classes: lists (class c's rows from lists + c*m) and counts cls[0..NCLS);
-// rows without products get nnz 0; hst[0] = the class-H rows' products, hst[1]
-// = the largest row's products (the routing statistics), hst[2] = all products,
-// hst[3] = the products of hub rows (past kRowsHubProducts), hst[4] = the
-// class-H rows with more than OW_RUNS runs, hst[8] = the class-H rows'
-// products past OW_CH (the one-walk rows' scratch)
-// (*Etot, copied so that one read-back brings everything); rnnz[m] = 0 (the
-// row pointers' n+1 slot).  A workgroup per
+// rows -> classes: lists (class c's rows from lists + c*m), their counts and
+// the routing statistics in *cls (RowsCounters; products = *Etot, copied so
+// that one read-back brings everything); rows without products get nnz 0;
+// rnnz[m] = 0 (the row pointers' n+1 slot).  A workgroup per
 // BIN_ROWS rows: its counts first (one atomic per class), then its rows in
 // order into the reserved slots.
 __global__ __launch_bounds__(WG) void k_rows_bin(const int *rpA, int m, const long long *E, const long long *Etot,
-                                                 int *rnnz, int4 *lists, int *cls, long long *soff,
-                                                 unsigned long long *hst, const int *spart, int snb, int *sflag) {
+                                                 int *rnnz, int4 *lists, RowsCounters *cls, long long *soff,
+                                                 const int *spart, int snb, int *sflag) {
     __shared__ int gb[NCLS];
     __shared__ long long red64[WAVES];
     constexpr int RPT = BIN_ROWS / WG;  // rows per thread: every load of a sweep issued together
@@ -276,7 +205,7 @@ __global__ __launch_bounds__(WG) void k_rows_bin(const int *rpA, int m, const lo
     const int tid = threadIdx.x, lane = lane_id(), wv = wave_id();
     const int r0 = blockIdx.x * BIN_ROWS, r1 = min(m, r0 + BIN_ROWS);
     if (blockIdx.x == 0 && tid == 0) {
-        hst[2] = (unsigned long long)*Etot;
+        cls->products = (unsigned long long)*Etot;
         rnnz[m] = 0;
     }
     if (blockIdx.x == 0 && spart) {  // B's sortedness: the shares' sum (dev_rows_sorted_shares)
@@ -329,11 +258,11 @@ __global__ __launch_bounds__(WG) void k_rows_bin(const int *rpA, int m, const lo
     __syncthreads();
     if (tid == 0) {
         for (int w = 1; w < WAVES; ++w) pmax = max(pmax, red64[w]);
-        if (hp) atomicAdd(&hst[0], (unsigned long long)hp);
-        if (pmax) atomicMax(&hst[1], (unsigned long long)pmax);
-        if (drp) atomicAdd(&hst[3], (unsigned long long)drp);
-        if (hubr) atomicAdd(&hst[4], (unsigned long long)hubr);
-        if (hbig) atomicAdd(&hst[8], (unsigned long long)hbig);
+        if (hp) atomicAdd(&cls->hprod, (unsigned long long)hp);
+        if (pmax) atomicMax(&cls->pmax, (unsigned long long)pmax);
+        if (drp) atomicAdd(&cls->hubprod, (unsigned long long)drp);
+        if (hubr) atomicAdd(&cls->hk, (unsigned long long)hubr);
+        if (hbig) atomicAdd(&cls->hbig, (unsigned long long)hbig);
     }
     // the list slots with two barriers (one sweep per row slot u had cost two
     // each: 16 on a workgroup of 8 row slots): per (u, class) each wave's count
@@ -359,7 +288,7 @@ __global__ __launch_bounds__(WG) void k_rows_bin(const int *rpA, int m, const lo
                 wcu[u][tid][w] = run;
                 run += v;
             }
-        gb[tid] = run ? atomicAdd(&cls[tid], run) : 0;
+        gb[tid] = run ? atomicAdd(&cls->ncls[tid], run) : 0;
     }
     __syncthreads();
 #pragma unroll
@@ -377,10 +306,10 @@ __global__ __launch_bounds__(WG) void k_rows_bin(const int *rpA, int m, const lo
 // started last set the class's tail (row order: ~30 % over the longest-first
 // makespan on webbase).  Past OH_MAX rows the list keeps row order.
 constexpr int OH_NT = 1024, OH_PER = 8, OH_MAX = OH_NT * OH_PER, OH_NB = 64;
-__global__ __launch_bounds__(OH_NT) void k_rows_order_h(const long long *E, const int *cls, int4 *list) {
+__global__ __launch_bounds__(OH_NT) void k_rows_order_h(const long long *E, const int *nrows, int4 *list) {
     __shared__ int cnt[OH_NB];
     const int tid = threadIdx.x;
-    const int n = cls[NCLS - 1];
+    const int n = *nrows;
     if (n < 2 || n > OH_MAX) return;  // (workgroup-uniform)
     if (tid < OH_NB) cnt[tid] = 0;
     __syncthreads();
@@ -1122,20 +1051,6 @@ __device__ __forceinline__ void batch_walk(const RowsArgs &g, int nb, int q0, in
     }
 }
 
-// ranks inside a window: blk[w / RH_BLK] + g4[w / 4] + the bits of the
-// group's earlier words + the bits below c in its word
-__device__ __forceinline__ int bm_rank(const u64 *bm, const u16 *g4, const int *blk, long long c) {
-    const int w = (int)(c >> 6), gi = w >> 2, sub = w & 3;
-    const ulonglong2 lo = reinterpret_cast<const ulonglong2 *>(bm)[gi * 2];
-    const ulonglong2 hi = reinterpret_cast<const ulonglong2 *>(bm)[gi * 2 + 1];
-    const u64 word = sub == 0 ? lo.x : sub == 1 ? lo.y : sub == 2 ? hi.x : hi.y;
-    int rk = blk[w / RH_BLK] + g4[gi] + __popcll(word & ((1ull << (c & 63)) - 1ull));
-    rk += sub > 0 ? __popcll(lo.x) : 0;
-    rk += sub > 1 ? __popcll(lo.y) : 0;
-    rk += sub > 2 ? __popcll(hi.x) : 0;
-    return rk;
-}
-
 __global__ __launch_bounds__(RH_NT) void k_rows_bitmap(RowsArgs g, int *Tc, double *Tx, int *Tr,
                                                       unsigned long long *tcur) {
     {  // (hub rows, past kRowsHubProducts: the windowed or the DR kernels')
@@ -1304,8 +1219,8 @@ __global__ __launch_bounds__(RH_NT) void k_rows_bitmap(RowsArgs g, int *Tc, doub
         RP(6);
         int rk[RH_PPT];
 #pragma unroll
-        for (int j = 0; j < RH_PPT; ++j) rk[j] = cc[j] >= 0 ? bm_rank(bm, g4, blk, cc[j]) : 0;
-        for (int q = OW_CH + tid; q < P; q += RH_NT) Tr[toff + q] = bm_rank(bm, g4, blk, Tc[toff + q]);
+        for (int j = 0; j < RH_PPT; ++j) rk[j] = cc[j] >= 0 ? bitmap_rank<RH_BLK>(bm, g4, blk, cc[j]) : 0;
+        for (int q = OW_CH + tid; q < P; q += RH_NT) Tr[toff + q] = bitmap_rank<RH_BLK>(bm, g4, blk, Tc[toff + q]);
         RP(8);
         __syncthreads();  // (every bitmap read done: its LDS becomes the columns, then the values)
         RP(9);
@@ -1475,10 +1390,10 @@ __device__ __forceinline__ long long w_block_sum(long long x, long long *red) {
 
 // a workgroup per class-H row i.  Outputs (zero unless a W row): wnw[i] units,
 // wnch[i] chunks, wlo[i] first column, wwb[i] window bits;
-// wst[0] += W rows' products, wst[1] / wst[2] += DR rows' products / rows.
+// wst: += the W rows' products, the DR rows' products and count.
 __global__ __launch_bounds__(W_NT) void k_rows_wplan(RowsArgs g, int bn, long long unit, int *wnw, int *wnch,
                                                     int *wlo, int *wwb, long long *wmat,
-                                                    unsigned long long *wst, long long *soff) {
+                                                    HubCounters *wst, long long *soff) {
     constexpr int NW = W_NT / 64;
     __shared__ int red[2 * NW];
     __shared__ long long red64[NW];
@@ -1558,10 +1473,10 @@ __global__ __launch_bounds__(W_NT) void k_rows_wplan(RowsArgs g, int bn, long lo
         wwb[i] = wb;
         wmat[i] = (long long)nch * nw;
         if (nw) soff[le.x] = -1;  // (the compaction skips the row: k_rows_wunit<1> writes it)
-        if (pw) atomicAdd(&wst[0], (unsigned long long)pw);
+        if (pw) atomicAdd(&wst->wprod, (unsigned long long)pw);
         if (dr) {
-            atomicAdd(&wst[1], (unsigned long long)P);
-            atomicAdd(&wst[2], 1ull);
+            atomicAdd(&wst->drprod, (unsigned long long)P);
+            atomicAdd(&wst->ndr, 1ull);
         }
     }
 }
@@ -1660,9 +1575,9 @@ struct WUnit {
 // per W row (a workgroup per class-H row): out[u] = exclusive scan of in[u]
 // over the row's units; rnnz (optional) gets the row's total; rec (optional,
 // with wlo, wwb) the units' work records, and the fill lists: units of 1 ..
-// WS_CAP products appended to ulist (*lcnt64 bits 0..20: the sort fill's); for
+// WS_CAP products appended to ulist (*lcnt64's FillSizes::sort); for
 // the bitmap fill, units past W_RPT * WU_NT products to the back of ulist2,
-// ulist2[nu - 1 - i] (bits 21..41), the others to its front (bits 42..62) -- the
+// ulist2[nu - 1 - i] (heavy), the others to its front (mid) -- the
 // longest units dispatched first, so that none starts at the fill's end
 __global__ __launch_bounds__(W_NT) void k_rows_wscan(RowsArgs g, const int *ubase, const int *in, int *out,
                                                     int *rnnz, WUnit *rec = nullptr, const int *wlo = nullptr,
@@ -1719,16 +1634,15 @@ __global__ __launch_bounds__(W_NT) void k_rows_wscan(RowsArgs g, const int *ubas
             nm += v[t] > WS_MAX && v[t] <= HEAVY;
         }
         const int is = wave_incl_scan_dpp(ns), ih = wave_incl_scan_dpp(nh), im = wave_incl_scan_dpp(nm);
-        // one atomic per wave for the three lists: 21-bit fields of a u64 (nu < 2^21,
-        // the host's condition); three same-address atomics per wave cost ~0.17 ms
+        // one atomic per wave for the three lists: the fields of a u64 (nu <
+        // kFillListMax, the host's condition); three same-address atomics per wave cost ~0.17 ms
         // per LiveJournal block
         unsigned long long old = 0;
         if (lane == 63 && (is | ih | im))
-            old = atomicAdd(lcnt64, (unsigned long long)is | ((unsigned long long)ih << 21) |
-                                        ((unsigned long long)im << 42));
+            old = atomicAdd(lcnt64, fill_sizes_pack(is, ih, im));
         old = ((unsigned long long)__shfl((int)(old >> 32), 63, 64) << 32) | (u32)__shfl((int)old, 63, 64);
-        int ps = (int)(old & 0x1fffff) + is - ns, ph = (int)((old >> 21) & 0x1fffff) + ih - nh,
-            pm = (int)(old >> 42) + im - nm;
+        const FillSizes before = fill_sizes_unpack(old);
+        int ps = before.sort + is - ns, ph = before.heavy + ih - nh, pm = before.mid + im - nm;
 #pragma unroll
         for (int t = 0; t < PT; ++t) {
             const int w = tid * PT + t;
@@ -1781,19 +1695,6 @@ __global__ __launch_bounds__(W_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
             g.Sval[o] = x;
         }
     }, rm, red);
-}
-
-// rank of column c inside a unit's window (bitmap bm, block and group prefixes)
-__device__ __forceinline__ int w_rank(const u64 *bm, const u16 *g4, const int *blk, int c) {
-    const int w = c >> 6, gi = w >> 2, sub = w & 3;
-    const ulonglong2 lo = reinterpret_cast<const ulonglong2 *>(bm)[gi * 2];
-    const ulonglong2 hi = reinterpret_cast<const ulonglong2 *>(bm)[gi * 2 + 1];
-    const u64 word = sub == 0 ? lo.x : sub == 1 ? lo.y : sub == 2 ? hi.x : hi.y;
-    int rk = blk[w / W_BLK] + g4[gi] + __popcll(word & ((1ull << (c & 63)) - 1ull));
-    rk += sub > 0 ? __popcll(lo.x) : 0;
-    rk += sub > 1 ? __popcll(lo.y) : 0;
-    rk += sub > 2 ? __popcll(hi.x) : 0;
-    return rk;
 }
 
 // a workgroup per unit u (its record R: bucket of R.n products at R.s0, window
@@ -1909,7 +1810,7 @@ __global__ __launch_bounds__(NT) void k_rows_wunit(RowsArgs g, const WUnit *urec
     RP(2);
     int rk[W_RPT];
 #pragma unroll
-    for (int t = 0; t < W_RPT; ++t) rk[t] = cc[t] >= 0 ? w_rank(bm, g4, blk, cc[t]) : 0;
+    for (int t = 0; t < W_RPT; ++t) rk[t] = cc[t] >= 0 ? bitmap_rank<W_BLK>(bm, g4, blk, cc[t]) : 0;
     static_assert(2 * W_WORDS >= W_RPT * NT, "the bitmap's LDS holds a column per rank (wn <= n)");
     if (n <= W_RPT * NT) {  // (workgroup-uniform) every product in registers
         // the bitmap is done with once the ranks are: its LDS takes each rank's
@@ -1957,7 +1858,7 @@ __global__ __launch_bounds__(NT) void k_rows_wunit(RowsArgs g, const WUnit *urec
             if (cc[t] >= 0 && (unsigned)(rk[t] - r0) < (unsigned)W_VCAP) atomicAdd(&vals[rk[t] - r0], xx[t]);
         for (int q = W_RPT * NT + tid; q < n; q += NT) {
             const int c = (int)(g.Scol[s0 + q] - wlo0);
-            const int rq = w_rank(bm, g4, blk, c) - r0;
+            const int rq = bitmap_rank<W_BLK>(bm, g4, blk, c) - r0;
             if ((unsigned)rq < (unsigned)W_VCAP) atomicAdd(&vals[rq], g.Sval[s0 + q]);
         }
         __syncthreads();
@@ -1966,7 +1867,7 @@ __global__ __launch_bounds__(NT) void k_rows_wunit(RowsArgs g, const WUnit *urec
         for (int w = tid; w < nwd; w += NT) {
             u64 word = bm[w];
             if (!word) continue;
-            int r = w_rank(bm, g4, blk, w * 64);
+            int r = bitmap_rank<W_BLK>(bm, g4, blk, w * 64);
             if (r >= r1) continue;
             while (word) {
                 const int bit = __builtin_ctzll(word);
@@ -2511,39 +2412,11 @@ __global__ __launch_bounds__(WG) void k_rows_compact(int m, const int *cfirst, c
         }
 }
 
-// Two-launch exclusive scans (tile sums, then an apply that adds up the earlier
-// tiles' sums) for the other CSR paths; TSG_ERR_UNSUPPORTED past RS_INLINE_MAX
-// tiles (the caller then takes the generic scan).  Row pointers: n = m + 1,
-// nnz(C) (the last value) into the host-mapped *hnnz_dev.
-int dev_scan_i64_fused(Context &cx, long long *a, long n, hipStream_t s) {
-    const long nt = (n + RS_TILE - 1) / RS_TILE;
-    if (n <= 0) return TSG_OK;
-    if (nt > RS_INLINE_MAX) return TSG_ERR_UNSUPPORTED;
-    PoolScope ws(cx);
-    long long *part = nullptr;
-    TSG_TRY(ws.get(&part, (size_t)nt));
-    k_rows_count_sum<long long><<<(unsigned)nt, WG, 0, s>>>(a, n, part);
-    k_rows_scan_apply<long long, false><<<(unsigned)nt, WG, 0, s>>>(a, n, part, nullptr, 0, nullptr);
-    TSG_HIP(hipGetLastError());
-    return TSG_OK;  // (part returns here: stream-ordered reuse)
-}
-int dev_scan_rows_fused(Context &cx, int *rp, int m, int *hnnz_dev, hipStream_t s) {
-    const long n = (long)m + 1, nt = (n + RS_TILE - 1) / RS_TILE;
-    if (nt > RS_INLINE_MAX) return TSG_ERR_UNSUPPORTED;
-    PoolScope ws(cx);
-    int *part = nullptr;
-    TSG_TRY(ws.get(&part, (size_t)nt));
-    k_rows_count_sum<int><<<(unsigned)nt, WG, 0, s>>>(rp, n, part);
-    k_rows_scan_apply<int, true><<<(unsigned)nt, WG, 0, s>>>(rp, n, part, nullptr, m, hnnz_dev);
-    TSG_HIP(hipGetLastError());
-    return TSG_OK;  // (part returns here: stream-ordered reuse)
-}
-
 // Setup (stream-ordered, no host round trip): the entry table, its scan and the
-// classes; counts and statistics land in cx.pinned64[0..7) once the stream is synced.
+// classes; counts and statistics land in cx.slots->rows once the stream is synced.
 int dev_rows_setup_async(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, RowsPlan &p, hipStream_t s,
                          SortedShares *sh) {
-    static_assert(NCLS <= 8, "class counts in cls[0..8)");
+    static_assert(NCLS <= sizeof(RowsCounters::ncls) / sizeof(int), "a count per class");
     const int m = A.m;
     p = RowsPlan{};
     PoolScope ws(cx);
@@ -2551,20 +2424,15 @@ int dev_rows_setup_async(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B
     TSG_TRY(ws.get(&p.E, (size_t)A.nnz + 1));
     TSG_TRY(ws.get(&p.lists, (size_t)NCLS * (m > 0 ? m : 1)));
     TSG_TRY(ws.get(&p.soff, (size_t)m + 1));
-    // class counts [0..8), 5 u64 statistics [8..18), hub rows' cursors [18..22), the one-walk
-    // rows' scratch products (u64) [24..26) and its cursor [26..28)
-    TSG_TRY(ws.get(&p.cls, 32));
+    TSG_TRY(ws.get(&p.cls, 1));
     TSG_TRY(ws.get(&p.rowpointer, (size_t)m + 1));
-    unsigned long long *hst = reinterpret_cast<unsigned long long *>(p.cls + 8);
-    const long ntile = ((long)A.nnz + 1 + RS_TILE - 1) / RS_TILE;
-    if (ntile <= RS_INLINE_MAX) {  // entry table + tile sums, then the apply: two launches
+    if (scan_fuses((long)A.nnz + 1)) {  // entry table + tile sums, then the apply: two launches
+        const long ntile = scan_tiles((long)A.nnz + 1);
         long long *part = nullptr;
         TSG_TRY(ws.get(&part, (size_t)ntile));
         k_rows_entries_sum<<<(unsigned)ntile, WG, 0, s>>>(A.columnindex, A.nnz, B.rowpointer, p.ebnd, p.E, p.cls,
                                                           part);
-        k_rows_scan_apply<long long, false><<<(unsigned)ntile, WG, 0, s>>>(p.E, (long)A.nnz + 1, part, nullptr, 0,
-                                                                           nullptr);
-        TSG_HIP(hipGetLastError());
+        TSG_TRY(scan_apply_fused_i64(p.E, (long)A.nnz + 1, part, s));
         ws.put(part);  // (stream-ordered reuse)
     } else {
         k_rows_entries<<<grid_for((long)A.nnz + 1, WG, 16384), WG, 0, s>>>(A.columnindex, A.nnz, B.rowpointer,
@@ -2574,22 +2442,23 @@ int dev_rows_setup_async(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B
     }
     // (one workgroup at least: it writes the statistics and rowpointer[m])
     k_rows_bin<<<max(1, (m + BIN_ROWS - 1) / BIN_ROWS), WG, 0, s>>>(
-        A.rowpointer, m, p.E, p.E + A.nnz, p.rowpointer, p.lists, p.cls, p.soff, hst, sh ? sh->part : nullptr,
+        A.rowpointer, m, p.E, p.E + A.nnz, p.rowpointer, p.lists, p.cls, p.soff, sh ? sh->part : nullptr,
         sh ? sh->nb : 0, sh ? sh->dflag : nullptr);
     TSG_HIP(hipGetLastError());
-    TSG_HIP(hipMemcpyAsync(cx.pinned64, p.cls, 26 * sizeof(int), hipMemcpyDeviceToHost, s));
+    TSG_HIP(hipMemcpyAsync(&cx.slots->rows, p.cls, RowsCounters::kReadBytes, hipMemcpyDeviceToHost, s));
     keep_blocks(ws, p);
     return TSG_OK;
 }
 
 void dev_rows_setup_read(Context &cx, RowsPlan &p) {
-    for (int t = 0; t < NCLS; ++t) p.ncls[t] = reinterpret_cast<const int *>(cx.pinned64)[t];
-    p.hprod = cx.pinned64[4];
-    p.pmax = cx.pinned64[5];
-    p.products = cx.pinned64[6];
-    p.hubprod = cx.pinned64[7];
-    p.hk = cx.pinned64[8];
-    p.hbig = cx.pinned64[12];
+    const RowsCounters &h = cx.slots->rows;
+    for (int t = 0; t < NCLS; ++t) p.ncls[t] = h.ncls[t];
+    p.hprod = (long long)h.hprod;
+    p.pmax = (long long)h.pmax;
+    p.products = (long long)h.products;
+    p.hubprod = (long long)h.hubprod;
+    p.hk = (long long)h.hk;
+    p.hbig = (long long)h.hbig;
 }
 
 // routing: every product whose B rows are strictly column-sorted (class H's
@@ -2611,12 +2480,12 @@ struct HubSizes {
 // windowed (W) rows' arrays: per class-H row, per unit, per chunk
 struct WinRows {
     int *wnw = nullptr, *wnch = nullptr, *wlo = nullptr, *wwb = nullptr, *umap = nullptr;
-    int *ucnt = nullptr, *ubo = nullptr, *ucount = nullptr, *uoff = nullptr, *ulist = nullptr, *ulist2 = nullptr,
-        *lcnt = nullptr;  // (the lists' three sizes packed in one u64, 21 bits each)
+    int *ucnt = nullptr, *ubo = nullptr, *ucount = nullptr, *uoff = nullptr, *ulist = nullptr, *ulist2 = nullptr;
+    unsigned long long *lcnt = nullptr;  // the fill lists' three sizes (fill_sizes_pack)
     WUnit *urec = nullptr;
     long long *wmat = nullptr, *cmoff = nullptr;
     int *cbo = nullptr;
-    unsigned long long *wst = nullptr;
+    HubCounters *wst = nullptr;
     int4 *wchunks = nullptr;
     int nu = 0, nc = 0;  // units, chunks
 };
@@ -2631,8 +2500,7 @@ struct DomRuns {
 // how C is sized, and what the compaction needs of it
 struct CSizing {
     bool small = false;       // by the products, nnz(C) back with the call's final synchronisation
-    bool fused_scan = false;  // small with at most RS_INLINE_MAX tiles of row counts
-    long rtile = 0;
+    bool fused_scan = false;  // small, and the row counts took the fused scan (dev_scan_rows)
     long long nnz = 0, cap = 0;
     bool lknown = false;    // the windowed fill lists' sizes came back with the checked scan's total
     int *cfirst = nullptr;  // the compaction's chunk table
@@ -2648,8 +2516,8 @@ int rows_hub_plan(Context &cx, PoolScope &ws, const RowsArgs &g, int n7, int bn,
     TSG_TRY(ws.get(&w.wlo, (size_t)n7));
     TSG_TRY(ws.get(&w.wwb, (size_t)n7));
     TSG_TRY(ws.get(&w.wmat, (size_t)n7 + 1));
-    TSG_TRY(ws.get(&w.wst, 4));
-    TSG_HIP(hipMemsetAsync(w.wst, 0, 4 * sizeof(unsigned long long), s));
+    TSG_TRY(ws.get(&w.wst, 1));
+    TSG_HIP(hipMemsetAsync(w.wst, 0, sizeof(HubCounters), s));
     // (W_UNIT products per unit: 4,096 measured equal, 16,384 / 32,768 slower)
     k_rows_wplan<<<n7, W_NT, 0, s>>>(g, bn, W_UNIT, w.wnw, w.wnch, w.wlo, w.wwb, w.wmat, w.wst, soff);
     TSG_HIP(hipGetLastError());
@@ -2659,19 +2527,18 @@ int rows_hub_plan(Context &cx, PoolScope &ws, const RowsArgs &g, int n7, int bn,
     TSG_TRY(scan_exclusive_i32(cx, w.wnw, (long)n7 + 1, s));   // -> ubase
     TSG_TRY(scan_exclusive_i32(cx, w.wnch, (long)n7 + 1, s));  // -> cbase
     TSG_TRY(scan_exclusive_i64(cx, w.wmat, (long)n7 + 1, s));  // -> chunk x window offset matrix
-    TSG_HIP(hipMemcpyAsync(cx.pinned64 + 16, w.wst, 3 * sizeof(long long), hipMemcpyDeviceToHost, s));
-    TSG_HIP(hipMemcpyAsync(reinterpret_cast<int *>(cx.pinned64 + 20), w.wnw + n7, sizeof(int),
-                           hipMemcpyDeviceToHost, s));
-    TSG_HIP(hipMemcpyAsync(reinterpret_cast<int *>(cx.pinned64 + 21), w.wnch + n7, sizeof(int),
-                           hipMemcpyDeviceToHost, s));
-    TSG_HIP(hipMemcpyAsync(cx.pinned64 + 22, w.wmat + n7, sizeof(long long), hipMemcpyDeviceToHost, s));
+    HostSlots &hs = *cx.slots;
+    TSG_HIP(hipMemcpyAsync(&hs.hub, w.wst, offsetof(HubCounters, pad), hipMemcpyDeviceToHost, s));
+    TSG_HIP(hipMemcpyAsync(&hs.hub_units, w.wnw + n7, sizeof(int), hipMemcpyDeviceToHost, s));
+    TSG_HIP(hipMemcpyAsync(&hs.hub_chunks, w.wnch + n7, sizeof(int), hipMemcpyDeviceToHost, s));
+    TSG_HIP(hipMemcpyAsync(&hs.hub_nmat, w.wmat + n7, sizeof(long long), hipMemcpyDeviceToHost, s));
     TSG_TRY(stream_wait(s));
-    h.wprod = cx.pinned64[16];
-    h.nmat = cx.pinned64[22];
-    h.drprod = cx.pinned64[17];
-    h.ndr = cx.pinned64[18];
-    w.nu = *reinterpret_cast<const int *>(cx.pinned64 + 20);
-    w.nc = *reinterpret_cast<const int *>(cx.pinned64 + 21);
+    h.wprod = (long long)hs.hub.wprod;
+    h.nmat = hs.hub_nmat;
+    h.drprod = (long long)hs.hub.drprod;
+    h.ndr = (long long)hs.hub.ndr;
+    w.nu = hs.hub_units;
+    w.nc = hs.hub_chunks;
     return TSG_OK;
 }
 
@@ -2690,9 +2557,9 @@ int rows_win_prepare(PoolScope &ws, const RowsArgs &g, int n7, long long nmat, W
     TSG_TRY(ws.get(&w.urec, (size_t)nu));
     TSG_TRY(ws.get(&w.ulist, (size_t)nu));
     TSG_TRY(ws.get(&w.ulist2, (size_t)nu));
-    TSG_TRY(ws.get(&w.lcnt, 2));
+    TSG_TRY(ws.get(&w.lcnt, 1));
     TSG_HIP(hipMemsetAsync(w.ucnt, 0, (size_t)nu * sizeof(int), s));
-    TSG_HIP(hipMemsetAsync(w.lcnt, 0, 2 * sizeof(int), s));
+    TSG_HIP(hipMemsetAsync(w.lcnt, 0, sizeof(*w.lcnt), s));
     // (the run map of each walk step, not a binary search of the run table
     // per product: 2.75 vs 3.25 ms on the LiveJournal block)
     k_rows_wchunks<<<n7, WG, 0, s>>>(g, ubase, cbase, w.wmat, w.wchunks, w.cmoff, w.umap);
@@ -2700,8 +2567,7 @@ int rows_win_prepare(PoolScope &ws, const RowsArgs &g, int n7, long long nmat, W
     k_rows_wcount<<<nc, W_NT, 0, s>>>(g, w.wchunks, w.cmoff, w.wlo, w.wwb, ubase, w.ucnt, w.cbo);
     TSG_HIP(hipGetLastError());
     k_rows_wscan<<<n7, W_NT, 0, s>>>(g, ubase, w.ucnt, w.ubo, nullptr, w.urec, w.wlo, w.wwb,
-                                     nu < (1 << 21) ? w.ulist : nullptr, w.ulist2,
-                                     reinterpret_cast<unsigned long long *>(w.lcnt), nu);
+                                     nu < kFillListMax ? w.ulist : nullptr, w.ulist2, w.lcnt, nu);
     TSG_HIP(hipGetLastError());
     k_rows_wscatter<<<nc, W_NT, 0, s>>>(g, w.wchunks, w.cmoff, w.wlo, w.wwb, ubase, w.ubo, w.cbo);
     TSG_HIP(hipGetLastError());
@@ -2741,7 +2607,7 @@ int rows_w_dump(const WinRows &w, int n7, long long wprod, hipStream_t s) {
 
 // hub rows with a dominant run: their tables and exact counts
 // (per_row, TSG_DR_PER_ROW: the per-row chunks also below DR_GMAX rows -- a test of that path)
-int rows_dr_prepare(PoolScope &ws, const RowsArgs &g, int n7, long long *soff, int *cls, const HubSizes &h,
+int rows_dr_prepare(PoolScope &ws, const RowsArgs &g, int n7, long long *soff, RowsCounters *cls, const HubSizes &h,
                     bool per_row, DomRuns &d, hipStream_t s) {
     const long long ndr = h.ndr, nch = h.drprod / DR_CH + ndr;
     TSG_TRY(ws.get(&d.drows, (size_t)ndr));
@@ -2749,10 +2615,11 @@ int rows_dr_prepare(PoolScope &ws, const RowsArgs &g, int n7, long long *soff, i
     TSG_TRY(ws.get(&d.dchunks, (size_t)nch));
     TSG_TRY(ws.get(&d.dord, (size_t)ndr));
     const bool grouped = ndr <= DR_GMAX && !per_row;
-    k_rows_dr_prep<<<n7, DR_NT, 0, s>>>(g, soff, d.drows, d.dents, d.dord, d.dchunks, cls + 20, cls + 21, !grouped);
+    k_rows_dr_prep<<<n7, DR_NT, 0, s>>>(g, soff, d.drows, d.dents, d.dord, d.dchunks, &cls->dr_chunks, &cls->dr_rows,
+                                        !grouped);
     TSG_HIP(hipGetLastError());
     if (grouped) {
-        k_rows_dr_group<<<1, DR_NT, 0, s>>>(d.drows, cls + 21, d.dord, d.dchunks, cls + 20);
+        k_rows_dr_group<<<1, DR_NT, 0, s>>>(d.drows, &cls->dr_rows, d.dord, d.dchunks, &cls->dr_chunks);
         TSG_HIP(hipGetLastError());
     }
     d.drnch = nch;
@@ -2819,29 +2686,15 @@ int rows_scan_size_c(Context &cx, PoolScope &ws, const RowsPlan &p, int m, const
                      CSizing &z, hipStream_t s) {
     const long long products = p.products;
     const int nu = w.nu;
-    int *const hnnz = reinterpret_cast<int *>(cx.pinned64 + 15);
-    int *const hl = reinterpret_cast<int *>(cx.pinned64 + 24);  // the fill lists' sizes (a packed u64)
     if (z.small) {
-        if (z.fused_scan) {
-            // one launch of tile sums, then one apply that also fills the
-            // compaction's chunk table and reports nnz(C) through the
-            // host-mapped pinned64[15] (no copy back)
-            int *part = nullptr;
-            TSG_TRY(ws.get(&part, (size_t)z.rtile));
-            // the apply fills the compaction's chunk table, a row's chunks by
-            // one thread: fine for short rows, serial for hub rows (a 3.5 M-
-            // nonzero LiveJournal row: 1.7 K chunks, ~50 us) -- past 2^20
-            // products in a row, k_rows_cfirst (a thread per chunk) after it
-            if (p.pmax <= (1LL << 20))
-                TSG_TRY(ws.get(&z.cfirst, (size_t)((products + CP_CH - 1) / CP_CH) + 1));
-            k_rows_count_sum<int><<<(unsigned)z.rtile, WG, 0, s>>>(C.rowpointer, (long)m + 1, part);
-            k_rows_scan_apply<int, true><<<(unsigned)z.rtile, WG, 0, s>>>(
-                C.rowpointer, (long)m + 1, part, z.cfirst, m, reinterpret_cast<int *>(cx.dpinned64 + 15));
-            TSG_HIP(hipGetLastError());
-            ws.put(part);  // (stream-ordered reuse)
-        } else {
-            TSG_TRY(scan_exclusive_i32(cx, C.rowpointer, (long)m + 1, s));
-        }
+        // the fused scan's apply also fills the compaction's chunk table and
+        // reports nnz(C) through the host-mapped slot (no copy back).  The
+        // table's rows by one thread each: fine for short rows, serial for hub
+        // rows (a 3.5 M-nonzero LiveJournal row: 1.7 K chunks, ~50 us) -- past
+        // 2^20 products in a row, k_rows_cfirst (a thread per chunk) after it
+        if (scan_fuses((long)m + 1) && p.pmax <= (1LL << 20))
+            TSG_TRY(ws.get(&z.cfirst, (size_t)((products + CP_CH - 1) / CP_CH) + 1));
+        TSG_TRY(dev_scan_rows(cx, C.rowpointer, m, z.cfirst, &cx.dslots->nnz_c, s, &z.fused_scan));
         if (ws.get(&C.columnindex, (size_t)products + 1) != TSG_OK ||
             ws.get(&C.value, (size_t)products + 1) != TSG_OK) {
             ws.put(C.columnindex);
@@ -2849,17 +2702,18 @@ int rows_scan_size_c(Context &cx, PoolScope &ws, const RowsPlan &p, int m, const
             z.small = false;  // (the scan's total is read back below)
             if (z.fused_scan) {
                 TSG_TRY(stream_wait(s));
-                C.nnz = *hnnz;
+                C.nnz = cx.slots->nnz_c;
             } else {
                 TSG_TRY(read_i32(cx, C.rowpointer + m, &C.nnz, s));
             }
             z.nnz = C.nnz;
         }
     } else {  // the checked scan (nnz(C) past int32 fails)
-        if (nu > 0 && nu < (1 << 21))  // (the fill lists' sizes come back with the scan's total)
-            TSG_HIP(hipMemcpyAsync(hl, w.lcnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        if (nu > 0 && nu < kFillListMax)  // (the fill lists' sizes come back with the scan's total)
+            TSG_HIP(hipMemcpyAsync(&cx.slots->fill_sizes, w.lcnt, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                   s));
         TSG_TRY(scan_exclusive_i32_total(cx, C.rowpointer, (long)m + 1, s, &z.nnz));
-        z.lknown = nu > 0 && nu < (1 << 21);
+        z.lknown = nu > 0 && nu < kFillListMax;
         if (z.nnz > 0x7fffffffLL) return TSG_ERR_OVERFLOW;
     }
     z.cap = z.small ? products : z.nnz;
@@ -2873,14 +2727,14 @@ int rows_scan_size_c(Context &cx, PoolScope &ws, const RowsPlan &p, int m, const
 // the windowed rows' nonzeros straight into C (the compaction skips those rows)
 // and the dominant-run rows' (their counts exact since k_rows_dr_prep)
 int rows_hub_fills(Context &cx, const RowsArgs &g7, const tsg_dev_csr &C, const WinRows &w, const DomRuns &d,
-                   int *cls, bool lknown, hipStream_t s) {
+                   RowsCounters *cls, bool lknown, hipStream_t s) {
     const int nu = w.nu;
     if (nu > 0) {
         if (lknown) {
             // the list sizes came back with the checked scan's total: the bitmap
             // fill over its list (the longest units first), the sort fill over its
-            const unsigned long long pk = *reinterpret_cast<const unsigned long long *>(cx.pinned64 + 24);
-            const int gs = (int)(pk & 0x1fffff), gh = (int)((pk >> 21) & 0x1fffff), gb = gh + (int)(pk >> 42);
+            const FillSizes fs = fill_sizes_unpack(cx.slots->fill_sizes);
+            const int gs = fs.sort, gh = fs.heavy, gb = fs.heavy + fs.mid;
             if (gb > 0)
                 k_rows_wunit<1, WU_NT><<<gb, WU_NT, 0, s>>>(g7, w.urec, w.ucount, w.uoff, C.rowpointer,
                                                            C.columnindex, C.value, w.ulist2, nu - 1, gh);
@@ -2899,7 +2753,7 @@ int rows_hub_fills(Context &cx, const RowsArgs &g7, const tsg_dev_csr &C, const 
     if (d.drnch > 0) {
         // (persistent: the grouped chunk count, under drnch, is known on the device only)
         k_rows_dr_fill<<<(unsigned)std::min<long long>(d.drnch, 1024), DR_NT, 0, s>>>(
-            g7, C.rowpointer, C.columnindex, C.value, d.drows, d.dents, d.dord, d.dchunks, cls + 20);
+            g7, C.rowpointer, C.columnindex, C.value, d.drows, d.dents, d.dord, d.dchunks, &cls->dr_chunks);
         TSG_HIP(hipGetLastError());
     }
     return TSG_OK;
@@ -2958,7 +2812,7 @@ int dev_rows_run(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const 
 #endif
     RowsArgs g{A.rowpointer, A.value, p.ebnd, p.E, B.columnindex, B.value, nullptr, 0, C.rowpointer, Scol, Sval};
     if (ncls[7] >= 2 && ncls[7] <= OH_MAX) {
-        k_rows_order_h<<<1, OH_NT, 0, s>>>(p.E, p.cls, p.lists + (long)(NCLS - 1) * m);
+        k_rows_order_h<<<1, OH_NT, 0, s>>>(p.E, &p.cls->ncls[NCLS - 1], p.lists + (long)(NCLS - 1) * m);
         TSG_HIP(hipGetLastError());
     }
     HubSizes h;
@@ -2988,7 +2842,7 @@ int dev_rows_run(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const 
                 TSG_TRY(ws.get(&Ox, (size_t)p.hbig));
                 TSG_TRY(ws.get(&Or, (size_t)p.hbig));
             }
-            k_rows_bitmap<<<n7, RH_NT, 0, s>>>(g, Oc, Ox, Or, reinterpret_cast<unsigned long long *>(p.cls + 26));
+            k_rows_bitmap<<<n7, RH_NT, 0, s>>>(g, Oc, Ox, Or, &p.cls->ow_cursor);
             TSG_HIP(hipGetLastError());
         }
         if (h.drprod > 0) TSG_TRY(rows_dr_prepare(ws, g, n7, p.soff, p.cls, h, cx.knobs.dr_per_row, d, s));
@@ -3007,17 +2861,15 @@ int dev_rows_run(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const 
     // the large products' path, with its fill lists, on small ones)
     CSizing z;
     z.small = p.products <= 0x7fffffffLL && p.products * 12 <= kRowsProductSizedC && !cx.knobs.rows_checked_scan;
-    z.rtile = ((long)m + 1 + RS_TILE - 1) / RS_TILE;
-    z.fused_scan = z.small && z.rtile <= RS_INLINE_MAX;
     TSG_TRY(rows_scan_size_c(cx, ws, p, m, w, C, z, s));
     TSG_TRY(rows_hub_fills(cx, g7, C, w, d, p.cls, z.lknown, s));
     if (ev && fills) TSG_HIP(hipEventRecord(ev[5], s));
     TSG_TRY(rows_compact(ws, m, p.soff, Scol, Sval, C, z, s));
     if (z.small && !z.fused_scan)
-        TSG_HIP(hipMemcpyAsync(cx.pinned64 + 15, C.rowpointer + m, sizeof(int), hipMemcpyDeviceToHost, s));
+        TSG_HIP(hipMemcpyAsync(&cx.slots->nnz_c, C.rowpointer + m, sizeof(int), hipMemcpyDeviceToHost, s));
     if (ev && cx.stage_ev) TSG_HIP(hipEventRecord(ev[3], s));
     TSG_TRY(stream_wait(s));
-    if (z.small) z.nnz = *reinterpret_cast<const int *>(cx.pinned64 + 15);
+    if (z.small) z.nnz = cx.slots->nnz_c;
     C.nnz = (int)z.nnz;
     ws.keep(C.columnindex);
     ws.keep(C.value);

@@ -87,6 +87,7 @@ typedef struct tsg_stats {
 #define TSG_PATH_ROWS 3   /* row merge: rows binned by products, B runs merged in LDS */
 #define TSG_PATH_NUMERIC 4 /* numeric-only run on a known C pattern (tsg_dev_numeric_run) */
 #define TSG_PATH_MASKED 5  /* masked run: A*B on a mask's pattern only (tsg_dev_masked_run) */
+#define TSG_PATH_SYMBOLIC 6 /* symbolic pass: C's pattern without values (tsg_dev_spgemm_symbolic) */
 
 /* ---------------- library / device ---------------- */
 const char *tsg_version(void);
@@ -176,6 +177,14 @@ int tsg_spgemm_csr_numeric(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatr
  * operands, creates a masked plan, runs it once and destroys it.  stats may be
  * NULL. */
 int tsg_spgemm_csr_masked(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, int mode, tsg_stats *stats);
+
+/* Symbolic product: C's structural pattern without values.  Uploads the
+ * patterns of A and B (their value fields are not read and may be NULL), runs
+ * tsg_dev_spgemm_symbolic (below) and downloads the result: C->m, n, nnz and
+ * C->rowpointer (malloc'd, m + 1), and for TSG_SYMBOLIC_PATTERN C->columnindex
+ * (malloc'd, strictly ascending per row); C->value is NULL (TSG_SYMBOLIC_COUNT:
+ * C->columnindex too).  stats may be NULL. */
+int tsg_spgemm_csr_symbolic(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, int mode, tsg_stats *stats);
 
 /* Frees every non-NULL pointer field and zeroes the struct (covers the
  * reference's matrix_destroy, src/csr2tile.h:509-518, and the CSR arrays). */
@@ -372,6 +381,42 @@ int tsg_dev_masked_run(tsg_context *ctx, tsg_masked_plan *plan, const double *a_
                        double *c_val, void *stream, tsg_stats *stats /*nullable*/);
 /* TSG_ERR_INVALID for a plan that is not alive on ctx (e.g. destroyed twice). */
 int tsg_dev_masked_plan_destroy(tsg_context *ctx, tsg_masked_plan *plan);
+
+/* ---- symbolic SpGEMM: C's pattern and row counts without values ----
+ * The first half of the symbolic / numeric split: the pattern that
+ * tsg_dev_numeric_plan_create and tsg_dev_masked_plan_create start from, and
+ * the exact nnz(C) before anything is computed.  Entry (i, j) is in C iff some
+ * k has A(i,k) and B(k,j) stored (no zero is dropped): element for element the
+ * rowpointer / columnindex of tsg_dev_spgemm for the same operands, columns
+ * strictly ascending per row, value == NULL.  The value fields of A and B are
+ * never read and may be NULL; their rows may be unsorted and may repeat a
+ * column.  Count-first: a count per row, a scan, then every column written once
+ * at its final place -- no values, no product-sized staging, no compaction.
+ * A and B are validated on the device before anything indexes with them, as
+ * the numeric plan validates them (rowpointer[0] == 0, non-decreasing,
+ * rowpointer[m] == nnz, columns in [0, n), A->n == B->m): a violation or an
+ * unknown mode returns TSG_ERR_INVALID.  nnz(C) > INT32_MAX returns
+ * TSG_ERR_OVERFLOW in both modes with the output zeroed, but info->nnzC holds
+ * the exact count.  Synchronous on return; the outputs are context-owned,
+ * valid until tsg_context_reset.  TSG_SYMBOLIC_COUNT: Cpattern->columnindex is
+ * NULL and nnz is set.  An empty C has columnindex NULL in both modes.
+ * stats (nullable): path = TSG_PATH_SYMBOLIC, nnzCub (= products), nnzC,
+ * t_e2e_ms, t_step3_kernel_ms (the count and fill kernels); the rest as in the
+ * numeric run. */
+#define TSG_SYMBOLIC_PATTERN 0  /* rowpointer and columnindex */
+#define TSG_SYMBOLIC_COUNT   1  /* rowpointer only: the count phase and the scan */
+
+typedef struct tsg_symbolic_info {
+    long long products;      /* sum over A entries of rowlen_B(col) */
+    long long nnzC;          /* exact, also when it does not fit int32 */
+    long long rows_class[4]; /* rows per class: packed / set / window / hub; rows without products are in none */
+    long long units;         /* work units of the classes that cut rows (window and hub) */
+    int b_rows_sorted;       /* what the call found (1: every B row strictly column-sorted) */
+} tsg_symbolic_info;
+
+int tsg_dev_spgemm_symbolic(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B,
+                            int mode, void *stream, tsg_dev_csr *Cpattern,
+                            tsg_symbolic_info *info /*nullable*/, tsg_stats *stats /*nullable*/);
 
 /* Copies between host and device (stream-ordered, synchronous on return). */
 int tsg_memcpy_h2d(tsg_context *ctx, void *dst, const void *src, size_t bytes, void *stream);

@@ -90,6 +90,16 @@ class MaskedInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SymbolicInfo(C.Structure):
+    """tsg_symbolic_info, field for field."""
+    _fields_ = [("products", C.c_longlong), ("nnzC", C.c_longlong), ("rows_class", C.c_longlong * 4),
+                ("units", C.c_longlong), ("b_rows_sorted", C.c_int)]
+
+    def as_dict(self):
+        return dict(products=self.products, nnzC=self.nnzC, rows_class=list(self.rows_class),
+                    units=self.units, b_rows_sorted=self.b_rows_sorted)
+
+
 class PoolStats(C.Structure):
     """tsg_pool_stats, field for field."""
     _fields_ = [(n, C.c_longlong) for n in ("live_blocks", "live_bytes", "reserved_bytes", "allocs")]
@@ -121,6 +131,8 @@ _SIGS = {
                                C.c_int),
     "tsg_spgemm_csr_masked": ([C.POINTER(SMatrix), C.POINTER(SMatrix), C.POINTER(SMatrix), C.c_int,
                                C.POINTER(Stats)], C.c_int),
+    "tsg_spgemm_csr_symbolic": ([C.POINTER(SMatrix), C.POINTER(SMatrix), C.POINTER(SMatrix), C.c_int,
+                                 C.POINTER(Stats)], C.c_int),
     "tsg_matrix_destroy": ([C.POINTER(SMatrix)], None),
     "tsg_context_create": ([C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "tsg_context_destroy": ([C.c_void_p], C.c_int),
@@ -150,6 +162,8 @@ _SIGS = {
     "tsg_dev_masked_run": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.POINTER(Stats)], C.c_int),
     "tsg_dev_masked_plan_destroy": ([C.c_void_p, C.c_void_p], C.c_int),
+    "tsg_dev_spgemm_symbolic": ([C.c_void_p, C.POINTER(DevCSR), C.POINTER(DevCSR), C.c_int, C.c_void_p,
+                                 C.POINTER(DevCSR), C.POINTER(SymbolicInfo), C.POINTER(Stats)], C.c_int),
     "tsg_memcpy_h2d": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
     "tsg_memcpy_d2h": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
     "tsg_memcpy_d2d": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),

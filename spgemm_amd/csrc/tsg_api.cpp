@@ -365,12 +365,17 @@ static void read_knobs(Context &cx) {
     k.tiled_csr = !is(getenv("TSG_TILED_CSR"), "0");
     k.rows_checked_scan = cs && cs[0] == '1';
     k.dr_per_row = getenv("TSG_DR_PER_ROW") != nullptr;
+    if (const char *hb = getenv("TSG_SYM_HUB_BYTES")) k.sym_hub_bytes = std::max(0ll, atoll(hb));
     cx.knobs = k;
     cx.stage_ev = se && se[0] == '1';
     // (the test-only knobs change what is timed: say so once, a silent A/B skew otherwise)
     static std::atomic_flag told = ATOMIC_FLAG_INIT;
     if ((k.rows_checked_scan || k.dr_per_row) && !quiet() && !told.test_and_set())
         fprintf(stderr, "[tsg] TSG_ROWS_CHECKED_SCAN / TSG_DR_PER_ROW set: test-only row-merge paths, "
+                        "not the production timings\n");
+    static std::atomic_flag told_sym = ATOMIC_FLAG_INIT;
+    if (k.sym_hub_bytes && !quiet() && !told_sym.test_and_set())
+        fprintf(stderr, "[tsg] TSG_SYM_HUB_BYTES set: test-only budget of the symbolic hub bitmaps, "
                         "not the production timings\n");
 }
 // The error contract of the tsg_dev_* calls (include/tsg.h): on an error the
@@ -1383,6 +1388,60 @@ int tsg_spgemm_csr_numeric(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatr
                 rc = TSG_ERR_HIP;
         }
         (void)tsg_dev_numeric_plan_destroy(lease.ctx(), plan);
+    }
+    return rc;
+}
+
+// ---- symbolic product: C's pattern without values (tsg_symbolic.hip)
+int tsg_dev_spgemm_symbolic(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B, int mode, void *stream,
+                            tsg_dev_csr *Cpattern, tsg_symbolic_info *info, tsg_stats *stats) {
+    if (Cpattern) *Cpattern = tsg_dev_csr{};
+    if (info) *info = tsg_symbolic_info{};
+    if (!ctx || !A || !B || !Cpattern) return TSG_ERR_INVALID;
+    Context &cx = ctx->cx;
+    read_knobs(cx);
+    auto h0 = std::chrono::steady_clock::now();
+    tsg_symbolic_info inf{};
+    const int rc = dev_result(dev_symbolic(cx, *A, *B, mode, *Cpattern, inf, (hipStream_t)stream, cx.ev), stream,
+                              Cpattern);
+    if (info) *info = inf;  // (on TSG_ERR_OVERFLOW too: the exact nnz(C))
+    if (rc == TSG_OK && stats) {
+        auto h1 = std::chrono::steady_clock::now();
+        tsg_stats st{};
+        st.numtileA = st.numtileB = st.numblkC = -1;
+        st.nnzCub = inf.products;
+        st.nnzC = inf.nnzC;
+        st.path = TSG_PATH_SYMBOLIC;
+        st.t_step3_kernel_ms = ev_ms(cx.ev[4], cx.ev[5]) + ev_ms(cx.ev[6], cx.ev[7]);
+        st.t_e2e_ms = std::chrono::duration<double, std::milli>(h1 - h0).count();
+        *stats = st;
+    }
+    return rc;
+}
+
+int tsg_spgemm_csr_symbolic(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, int mode, tsg_stats *stats) {
+    if (!A || !B || !C || A->n != B->m) return TSG_ERR_INVALID;
+    if (A->nnz < 0 || B->nnz < 0 || A->m < 0 || B->m < 0 || !A->rowpointer || !B->rowpointer) return TSG_ERR_INVALID;
+    if ((A->nnz && !A->columnindex) || (B->nnz && !B->columnindex)) return TSG_ERR_INVALID;
+    HostLease lease;
+    TSG_TRY(lease.acquire());
+    Context &cx = lease.cx();
+    hipStream_t s = lease.stream();
+    PoolScope ws(cx);  // (the uploads; what the dev_* call keeps returns with the lease)
+    tsg_dev_csr dA{A->m, A->n, A->nnz, nullptr, nullptr, nullptr}, dB{B->m, B->n, B->nnz, nullptr, nullptr, nullptr};
+    tsg_dev_csr dC{};
+    TSG_TRY(upload(ws, &dA.rowpointer, A->rowpointer, (size_t)A->m + 1, s));
+    TSG_TRY(upload(ws, &dA.columnindex, A->columnindex, (size_t)A->nnz, s));
+    TSG_TRY(upload(ws, &dB.rowpointer, B->rowpointer, (size_t)B->m + 1, s));
+    TSG_TRY(upload(ws, &dB.columnindex, B->columnindex, (size_t)B->nnz, s));
+    TSG_HIP(hipStreamSynchronize(s));
+    int rc = tsg_dev_spgemm_symbolic(lease.ctx(), &dA, &dB, mode, s, &dC, nullptr, stats);
+    if (rc == TSG_OK) {
+        memset(C, 0, sizeof(*C));
+        C->m = dC.m; C->n = dC.n; C->nnz = dC.nnz;
+        rc = download(&C->rowpointer, dC.rowpointer, (size_t)dC.m + 1, s);
+        if (rc == TSG_OK && dC.columnindex) rc = download(&C->columnindex, dC.columnindex, (size_t)dC.nnz, s);
+        if (rc == TSG_OK && hipStreamSynchronize(s) != hipSuccess) rc = TSG_ERR_HIP;
     }
     return rc;
 }

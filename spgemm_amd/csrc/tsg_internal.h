@@ -68,6 +68,7 @@ struct Knobs {
     bool tiled_csr = true;           // TSG_TILED_CSR=0: tsg_tilespgemm keeps the tile-payload kernels
     bool rows_checked_scan = false;  // TSG_ROWS_CHECKED_SCAN=1 (tests): the checked scan whatever the size
     bool dr_per_row = false;         // TSG_DR_PER_ROW (tests): per-row chunks also below DR_GMAX rows
+    long long sym_hub_bytes = 0;     // TSG_SYM_HUB_BYTES (tests): the symbolic hub bitmaps' byte budget (0: kSymHubBitmapBytes)
 };
 
 // The row-merge setup's device counters (RowsPlan::cls).  The entry kernels zero
@@ -110,6 +111,15 @@ struct HubCounters {
     unsigned long long pad;
 };
 
+// the symbolic pass's device counters (tsg_symbolic.hip, k_sym_classify)
+struct SymCounters {
+    int nlist[8];                   // rows per launch list (kSymLists of them)
+    unsigned long long products;    // all element products
+    unsigned long long win_units;   // the window class's (row, window) units (host side: read from their scan)
+    unsigned long long hub_units;   // the hub class's product chunks
+    unsigned long long pad;
+};
+
 // The windowed fill lists' three sizes in one u64 (one atomic per wave instead
 // of three): 21 bits each, so fewer than kFillListMax units.
 constexpr int kFillListBits = 21, kFillListMax = 1 << kFillListBits;
@@ -143,6 +153,7 @@ struct HostSlots {
     int hub_units, hub_chunks;     //   the unit and chunk lists' sizes,
     long long hub_nmat;            //   the chunk x window offset matrix's
     unsigned long long fill_sizes; // the windowed fill lists' sizes (fill_sizes_pack)
+    SymCounters sym;               // dev_symbolic: the class counts and unit totals
 };
 
 struct Context {
@@ -218,7 +229,7 @@ class PoolScope {
 };
 
 // ---- launchers (all stream-ordered, no sync; in tsg_device.hip unless a
-// comment names tsg_band, tsg_rows, tsg_ctiles, tsg_tile_steps, tsg_numeric or tsg_masked) ----
+// comment names tsg_band, tsg_rows, tsg_ctiles, tsg_tile_steps, tsg_numeric, tsg_masked or tsg_symbolic) ----
 // Exclusive scan in place over n elements (a[n-1] ends up = sum of a[0..n-2]
 // when the caller stored 0 there, i.e. the reference's "n+1 scan" idiom): the
 // generic three stages.
@@ -426,6 +437,8 @@ struct NumericPlan {
 // in range, Cp's columns strictly ascending per row; *b_sorted: whether B's are
 int dev_numeric_validate(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &Cp,
                          bool *b_sorted, hipStream_t s);
+// the same for the operands alone (the symbolic pass: there is no C pattern yet)
+int dev_operands_validate(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, bool *b_sorted, hipStream_t s);
 // skip (optional, host, one byte per row): rows with a non-zero byte go to the
 // never-launched list kNumLists whatever their class -- a run leaves their
 // c_val alone (the masked plan's rows of the dot leg).  validated (optional):
@@ -469,6 +482,45 @@ int dev_masked_plan_create(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr 
 int dev_masked_run(Context &cx, MaskedPlan &p, const double *a_val, const double *b_val, double *c_val,
                    hipStream_t s, hipEvent_t *ev);
 void dev_masked_plan_free(MaskedPlan &p);
+
+// symbolic product (tsg_symbolic.hip): C's row pointers
+// and, in TSG_SYMBOLIC_PATTERN mode, its columns, count-first: count per row,
+// scan, then every column written once at its final place.  No values, no
+// product-sized staging.  Rows are classed at call time by P, their element
+// products (an upper bound of the row's length); rows without products are in
+// no class:
+//   0 packed  P <= kSymPackedProducts  16 lanes per row: the products' columns in a
+//             32-int LDS slice, repeats dropped and survivors ranked by comparison
+//   1 set     P <= kSymSetProducts     an LDS hash set of 2 P slots, sorted by the
+//             fill: a wave per row up to kSymSetWaveProducts (4 KiB of LDS per
+//             row), a workgroup per row past it (32 KiB)
+//   2 window  P <= kSymWindowProducts  units of (row, window of kSymWindow columns):
+//             a kSymWindow / 8-byte LDS bitmap per unit (16 KiB: 8 workgroups, every
+//             wave slot of a CU), popcount = the unit's count, bit rank = position
+//   3 hub     the rest: chunks of at most kSymHubUnitProducts products set bits in an
+//             n-bit bitmap per row in global memory; the rows go in batches whose
+//             bitmaps stay within kSymHubBitmapBytes (one row's, where that is larger)
+constexpr long long kSymPackedProducts = 32, kSymSetWaveProducts = 512, kSymSetProducts = 4096,
+                    kSymWindowProducts = 65536;
+constexpr int kSymWindow = 131072;
+constexpr int kSymHubUnitProducts = 4096;
+constexpr long long kSymHubBitmapBytes = 64ll << 20;
+constexpr long long kSymMaxWinUnits = 1ll << 30;  // (row, window) units at most: TSG_ERR_OVERFLOW past it
+enum { kSymListPacked = 0, kSymListSetWave, kSymListSetWg, kSymListWindow, kSymListHub, kSymLists };
+__host__ __device__ inline int symbolic_row_list(long long products) {  // -1: no products, nothing to launch
+    return products <= 0                     ? -1
+           : products <= kSymPackedProducts  ? kSymListPacked
+           : products <= kSymSetWaveProducts ? kSymListSetWave
+           : products <= kSymSetProducts     ? kSymListSetWg
+           : products <= kSymWindowProducts  ? kSymListWindow
+                                             : kSymListHub;
+}
+// Validates A and B as the numeric plan does, then runs the pass; synchronous.
+// On TSG_ERR_OVERFLOW (nnz(C) past int32) info->nnzC still holds the exact
+// count.  ev: [4]..[5] bracket the count kernels, [6]..[7] the fill kernels
+// (recorded in both modes).
+int dev_symbolic(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, int mode, tsg_dev_csr &C,
+                 tsg_symbolic_info &info, hipStream_t s, hipEvent_t *ev);
 
 // read a device int / long long synchronously through pinned memory
 int read_i32(Context &cx, const int *d, int *h, hipStream_t s);

@@ -383,34 +383,51 @@ void dev_numeric_plan_free(NumericPlan &p) {
     p.hmiss = nullptr;
 }
 
-int dev_numeric_validate(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &Cp,
-                         bool *b_sorted, hipStream_t s) {
-    if (!shape_ok(A) || !shape_ok(B) || !shape_ok(Cp)) return TSG_ERR_INVALID;
-    if (A.n != B.m || Cp.m != A.m || Cp.n != B.n) return TSG_ERR_INVALID;
+// the validation of A and B, and of a C pattern where there is one (Cp null: the
+// symbolic pass, which has none yet)
+static int validate_patterns(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr *Cp,
+                             bool *b_sorted, hipStream_t s) {
+    if (!shape_ok(A) || !shape_ok(B) || (Cp && !shape_ok(*Cp))) return TSG_ERR_INVALID;
+    if (A.n != B.m || (Cp && (Cp->m != A.m || Cp->n != B.n))) return TSG_ERR_INVALID;
+    const tsg_dev_csr *mats[3] = {&A, &B, Cp};
+    const int nmat = Cp ? 3 : 2;
     PoolScope ws(cx);  // (the temporaries: returned to the pool on every way out)
     int *bad = nullptr;
     TSG_TRY(ws.get(&bad, 4));
     int hbad[2] = {0, 0};
     TSG_HIP(hipMemsetAsync(bad, 0, 4 * sizeof(int), s));
     // 1. row pointers, before anything indexes with them
-    for (const tsg_dev_csr *M : {&A, &B, &Cp})
+    for (int i = 0; i < nmat; ++i) {
+        const tsg_dev_csr *M = mats[i];
         k_num_check_rp<<<grid_for((long)M->m + 1, WG, 2048), WG, 0, s>>>(M->rowpointer, M->m, M->nnz, bad);
+    }
     TSG_HIP(hipGetLastError());
     TSG_HIP(hipMemcpyAsync(hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
     TSG_TRY(stream_wait(s));
     if (hbad[0]) return TSG_ERR_INVALID;
     // 2. columns in range; C's strictly ascending per row; whether B's are
-    for (const tsg_dev_csr *M : {&A, &B, &Cp})
+    for (int i = 0; i < nmat; ++i) {
+        const tsg_dev_csr *M = mats[i];
         if (M->nnz) k_num_check_cols<<<grid_for(M->nnz, WG, 2048), WG, 0, s>>>(M->columnindex, M->nnz, M->n, bad + 1);
+    }
     TSG_HIP(hipGetLastError());
-    bool csorted = false, bsorted = false;
-    TSG_TRY(dev_rows_sorted(cx, Cp, &csorted, s));
+    bool csorted = true, bsorted = false;
+    if (Cp) TSG_TRY(dev_rows_sorted(cx, *Cp, &csorted, s));
     TSG_TRY(dev_rows_sorted(cx, B, &bsorted, s));
     TSG_HIP(hipMemcpyAsync(hbad + 1, bad + 1, sizeof(int), hipMemcpyDeviceToHost, s));
     TSG_TRY(stream_wait(s));
     if (hbad[1] || !csorted) return TSG_ERR_INVALID;
     *b_sorted = bsorted;
     return TSG_OK;
+}
+
+int dev_numeric_validate(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &Cp,
+                         bool *b_sorted, hipStream_t s) {
+    return validate_patterns(cx, A, B, &Cp, b_sorted, s);
+}
+
+int dev_operands_validate(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, bool *b_sorted, hipStream_t s) {
+    return validate_patterns(cx, A, B, nullptr, b_sorted, s);
 }
 
 // Synchronous (the one-off cost): validation, then the binning on the host from

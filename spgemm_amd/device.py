@@ -9,7 +9,7 @@ import numpy as np
 
 import weakref
 
-from ._lib import DevCSR, MaskedInfo, NumericInfo, PoolStats, Stats, TsgError, check, lib
+from ._lib import DevCSR, MaskedInfo, NumericInfo, PoolStats, Stats, SymbolicInfo, TsgError, check, lib
 
 
 class DeviceCSR:
@@ -42,7 +42,8 @@ class DeviceCSR:
         return self.rowptr.data_ptr()
 
     def to_host(self):
-        return (self.m, self.n, self.rowptr.cpu().numpy(), self.col.cpu().numpy(), self.val.cpu().numpy())
+        return (self.m, self.n, self.rowptr.cpu().numpy(), self.col.cpu().numpy(),
+                self.val.cpu().numpy() if self.val is not None else None)
 
 
 class NumericPlan:
@@ -225,6 +226,35 @@ class Context:
                                                          C.byref(c), C.byref(st)))
         return c, (st if raw else st.as_dict())
 
+    def spgemm_symbolic(self, A, B, mode="pattern", stream=None):
+        """The structural pattern of A*B without values: (DevCSR struct with
+        context-owned row pointers and -- mode "pattern" -- columns, value null;
+        info dict; stats dict).  Valid until the next reset().  mode "count":
+        row pointers only (columnindex null, nnz set).  A's and B's values are
+        not read (DeviceCSRs with val=None are fine); their rows may be unsorted
+        and repeat columns.  Raises TsgError: TSG_ERR_INVALID for malformed
+        operands or an unknown mode; TSG_ERR_OVERFLOW when nnz(C) exceeds int32
+        -- the error's .info then still holds the exact nnzC."""
+        from .tilespgemm import SYMBOLIC_MODES
+        a, b, c, info, st = A.struct(), B.struct(), DevCSR(), SymbolicInfo(), Stats()
+        s = C.c_void_p(stream) if stream else None
+        md = SYMBOLIC_MODES.get(mode, mode)
+        rc = lib().tsg_dev_spgemm_symbolic(self.ptr, C.byref(a), C.byref(b), md if isinstance(md, int) else -1, s,
+                                           C.byref(c), C.byref(info), C.byref(st))
+        if rc != 0:
+            err = TsgError("tsg_dev_spgemm_symbolic", rc)
+            err.info = info.as_dict()
+            raise err
+        return c, info.as_dict(), st.as_dict()
+
+    def spgemm_plan(self, A, B, stream=None):
+        """A NumericPlan for C = A*B from the operands alone: the symbolic pass
+        gives C's pattern, which is copied into torch tensors (so it survives
+        reset()) and handed to numeric_plan.  The pattern is plan.Cpattern (a
+        DeviceCSR with val=None)."""
+        c, _, _ = self.spgemm_symbolic(A, B, "pattern", stream)
+        return self.numeric_plan(A, B, self.to_torch(c, device=A.rowptr.device, stream=stream), stream)
+
     def rows_sorted(self, M, stream=None):
         """whether every row of the device CSR M is strictly column-sorted"""
         m, out = M.struct(), C.c_int(0)
@@ -242,13 +272,15 @@ class Context:
         import torch
         rp = torch.empty(c.m + 1, dtype=torch.int32, device=device)
         ci = torch.empty(max(c.nnz, 1), dtype=torch.int32, device=device)
-        vv = torch.empty(max(c.nnz, 1), dtype=torch.float64, device=device)
+        vv = torch.empty(max(c.nnz, 1), dtype=torch.float64, device=device) if c.value or not c.nnz else None
         L = lib()
         check("tsg_memcpy_d2d", L.tsg_memcpy_d2d(self.ptr, rp.data_ptr(), c.rowpointer, 4 * (c.m + 1), stream))
-        if c.nnz:
+        ncol = c.nnz if c.columnindex else 0  # (a symbolic result: no values, in count mode no columns either)
+        if ncol:
             check("tsg_memcpy_d2d", L.tsg_memcpy_d2d(self.ptr, ci.data_ptr(), c.columnindex, 4 * c.nnz, stream))
+        if c.nnz and c.value:
             check("tsg_memcpy_d2d", L.tsg_memcpy_d2d(self.ptr, vv.data_ptr(), c.value, 8 * c.nnz, stream))
-        return DeviceCSR(c.m, c.n, rp, ci[: c.nnz], vv[: c.nnz])
+        return DeviceCSR(c.m, c.n, rp, ci[:ncol], vv[: c.nnz] if vv is not None else None)
 
     def view_torch(self, c):
         """Zero-copy torch views of a context-owned DevCSR (valid until the next
@@ -262,21 +294,27 @@ class Context:
 
         dev = torch.device("cuda", torch.cuda.current_device())
         rp = torch.as_tensor(_Buf(c.rowpointer, c.m + 1, "<i4"), device=dev)
-        if c.nnz:
+        if c.nnz and c.columnindex:
             ci = torch.as_tensor(_Buf(c.columnindex, c.nnz, "<i4"), device=dev)
-            vv = torch.as_tensor(_Buf(c.value, c.nnz, "<f8"), device=dev)
         else:
             ci = torch.empty(0, dtype=torch.int32, device=dev)
+        if c.nnz and c.value:
+            vv = torch.as_tensor(_Buf(c.value, c.nnz, "<f8"), device=dev)
+        elif c.nnz:
+            vv = None  # (a symbolic result: no values)
+        else:
             vv = torch.empty(0, dtype=torch.float64, device=dev)
         return DeviceCSR(c.m, c.n, rp, ci, vv)
 
     def to_host(self, c, stream=None):
         rp = np.empty(c.m + 1, dtype=np.int32)
         ci = np.empty(max(c.nnz, 1), dtype=np.int32)
-        vv = np.empty(max(c.nnz, 1), dtype=np.float64)
+        vv = np.empty(max(c.nnz, 1), dtype=np.float64) if c.value or not c.nnz else None
         L = lib()
         check("tsg_memcpy_d2h", L.tsg_memcpy_d2h(self.ptr, rp.ctypes.data, c.rowpointer, 4 * (c.m + 1), stream))
-        if c.nnz:
+        ncol = c.nnz if c.columnindex else 0  # (a symbolic result: no values, in count mode no columns either)
+        if ncol:
             check("tsg_memcpy_d2h", L.tsg_memcpy_d2h(self.ptr, ci.ctypes.data, c.columnindex, 4 * c.nnz, stream))
+        if c.nnz and c.value:
             check("tsg_memcpy_d2h", L.tsg_memcpy_d2h(self.ptr, vv.ctypes.data, c.value, 8 * c.nnz, stream))
-        return c.m, c.n, rp, ci[: c.nnz], vv[: c.nnz]
+        return c.m, c.n, rp, ci[:ncol], vv[: c.nnz] if vv is not None else None

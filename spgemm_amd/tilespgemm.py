@@ -34,6 +34,10 @@ PATH_MASKED = 5  # spgemm_masked / MaskedPlan.run
 # masked modes (include/tsg.h TSG_MASKED_*): per-row choice | all rows row-wise | all rows on the dot leg
 MASKED_AUTO, MASKED_ROWS, MASKED_DOT = 0, 1, 2
 MASKED_MODES = {"auto": MASKED_AUTO, "rows": MASKED_ROWS, "dot": MASKED_DOT}
+PATH_SYMBOLIC = 6  # spgemm_symbolic / Context.spgemm_symbolic
+# symbolic modes (include/tsg.h TSG_SYMBOLIC_*): row pointers and columns | row pointers only
+SYMBOLIC_PATTERN, SYMBOLIC_COUNT = 0, 1
+SYMBOLIC_MODES = {"pattern": SYMBOLIC_PATTERN, "count": SYMBOLIC_COUNT}
 
 
 def _view(ptr, n, dt):
@@ -184,6 +188,19 @@ def spgemm_masked(A, B, Cm, mode="auto"):
     check("tsg_spgemm_csr_masked", lib().tsg_spgemm_csr_masked(C.byref(A.s), C.byref(B.s), C.byref(Cm.s),
                                                                MASKED_MODES.get(mode, mode), C.byref(st)))
     return st.as_dict()
+
+
+def spgemm_symbolic(A, B, mode="pattern"):
+    """Symbolic product: the structural pattern of A*B without values (A's and
+    B's values are not read).  mode: "pattern" (row pointers and columns) or
+    "count" (row pointers only; or a TSG_SYMBOLIC_* value).  Returns (C Matrix
+    whose csr() has an empty value array -- and empty columns in count mode --,
+    stats dict)."""
+    Cm = Matrix()
+    st = Stats()
+    check("tsg_spgemm_csr_symbolic", lib().tsg_spgemm_csr_symbolic(C.byref(A.s), C.byref(B.s), C.byref(Cm.s),
+                                                                   SYMBOLIC_MODES.get(mode, mode), C.byref(st)))
+    return Cm, st.as_dict()
 
 
 def spgemm(A, B, tile_size_m=16, tile_size_n=16):

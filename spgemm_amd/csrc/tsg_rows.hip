@@ -13,16 +13,19 @@
 //   * entry table: each A entry's B range and a prefix of the element products
 //     over all entries (one int64 scan) -- a row's products, its staging
 //     offset and its runs' offsets are differences of that prefix;
-//   * rows binned by products (and runs) into four classes, each with a kernel
-//     shaped for it:
-//       S  <= 64 products : a wave per row, ranks by counting in registers;
-//       M1 <= 512         : a wave per row, pairwise merges of the runs in LDS;
-//       M2 <= 4,096       : a workgroup per row, the same merges;
+//   * rows binned by products (and runs) into eight classes (row_class), each
+//     with a kernel shaped for it:
+//       S16, S64 <= 16 / 64 products : a lane per product (16 lanes or a wave
+//                           per row), ranks by a one-key-per-lane sort network;
+//       M0..M4 <= 256 .. 4,096 : 64 .. 1,024 threads per row, packed (column,
+//                           position) keys sorted by a bitonic network in
+//                           registers and LDS (merge-path rounds for wide rows);
 //       H  longer         : a workgroup per row, a bitmap of a column window in
-//                           LDS, ranks by popcount, values by f64 atomics;
-//     the merge keys are (column, run, position) so they are unique and the
-//     merged order -- hence every sum's order -- is deterministic (class H's
-//     atomics are the exception);
+//                           LDS, ranks by popcount, values added in LDS (hub
+//                           rows: the dominant-run and windowed kernels);
+//     the sort keys are unique -- (column, lane) or (column, position) -- so
+//     the sorted order, hence every sum's order, is deterministic (class H's
+//     adds in LDS are the exception);
 //   * each row writes its nonzeros, column-sorted, to a staging area at the
 //     prefix of the products (products bound nnz), and its nnz; a scan of the
 //     counts gives the CSR row pointers, one streaming pass the final arrays.
@@ -353,8 +356,42 @@ template <int J, int N, class F> __device__ __forceinline__ void static_for(F &&
     }
 }
 
+// lane l's value of lane l ^ D (D a power of two below 64): DPP quad
+// permutes for 1 and 2, ds_swizzle's xor mode inside 32 lanes, ds_bpermute for 32
+template <int D> __device__ __forceinline__ u32 lane_xor(u32 v) {
+    if constexpr (D == 1) return (u32)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xf, 0xf, false);  // [1,0,3,2]
+    else if constexpr (D == 2) return (u32)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xf, 0xf, false);  // [2,3,0,1]
+    else if constexpr (D < 32) return (u32)__builtin_amdgcn_ds_swizzle((int)v, (D << 10) | 0x1f);
+    else return (u32)__shfl_xor((int)v, D, 64);
+}
+
+// med3(a, b, 0) = min(a, b) and med3(a, b, ~0u) = max(a, b): a compare-exchange
+// side picked by a selector (per lane or wave-uniform) is one v_med3_u32
+__device__ __forceinline__ u32 minmax_sel(u32 a, u32 b, u32 sel) { return min(max(a, b), max(min(a, b), sel)); }
+// bit B of v spread over the word: 0 or ~0u (one v_bfe_i32)
+template <int B> __device__ __forceinline__ u32 bit_fill(u32 v) { return (u32)((int)(v << (31 - B)) >> 31); }
+constexpr int ilog2_c(int v) { return v <= 1 ? 0 : 1 + ilog2_c(v >> 1); }
+
+// one key per lane, ascending over each group of G lanes (sl: the lane in its
+// group): a bitonic network of log2 G (log2 G + 1) / 2 stages -- 21 for a wave,
+// 10 inside 16 lanes -- each a lane exchange and one median of three with the
+// lane's selector, as bitonic_stage below
+template <int G, int K, int J> __device__ __forceinline__ void group_sort_merge(u32 &x, int sl) {
+    u32 w = (u32)sl;
+    if constexpr (K < G) w ^= bit_fill<ilog2_c(K)>((u32)sl);  // descending where sl & K
+    x = minmax_sel(x, lane_xor<J>(x), bit_fill<ilog2_c(J)>(w));
+    if constexpr (J > 1) group_sort_merge<G, K, J / 2>(x, sl);
+}
+template <int G, int K = G> __device__ __forceinline__ void group_sort(u32 &x, int sl) {
+    if constexpr (K > 2) group_sort<G, K / 2>(x, sl);
+    group_sort_merge<G, K, K / 2>(x, sl);
+}
+constexpr int SK_LB = 6;  // k_rows_small's packed keys: (column - the row's minimum) << SK_LB | lane
+
 // ---- classes S16 / S64: G lanes per row (64/G rows per wave), the products
-// one per lane, ranks by counting the group's smaller (column, lane) keys.
+// one per lane, ranked by sorting the group's packed (column, lane) keys, one
+// per lane (group_sort); a group whose column span does not fit the packed
+// key's 32 - SK_LB bits counts its smaller (column, lane) keys instead.
 // Each lane group takes U rows: the rows' loads (list, entries, B) are issued
 // stage by stage for all U together, so a wave waits for three dependent
 // memory round trips per U rows rather than per row (the classes are bound by
@@ -390,7 +427,9 @@ __global__ __launch_bounds__(WG) void k_rows_small(RowsArgs g) {
         be[u] = make_int2(0, 0);
         av[u] = 0.0;
         base[u] = 0;
-        if (live[u]) base[u] = g.E[a0[u]];  // (not waited for until the output)
+        // (not waited for until the output; S16 loads it after the ranks: held
+        // through them it cost the kernel its eighth wave per SIMD)
+        if (G == 64 && live[u]) base[u] = g.E[a0[u]];
         if (sl < k[u]) {
             be[u] = g.ebnd[a0[u] + sl];
             av[u] = g.vA[a0[u] + sl];
@@ -429,29 +468,68 @@ __global__ __launch_bounds__(WG) void k_rows_small(RowsArgs g) {
         ra[u] = __shfl(av[u], run, G);
         pp[u] = rb + sl - rs;
     }
-    u64 key[U];
+    // the lane's product: its column (the key is (column, lane); lanes past P
+    // hold ~0) and value
+    int kc[U];
     double x[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        key[u] = ~0ull;
+        kc[u] = -1;
         x[u] = 0.0;
         if (sl < P[u]) {
-            key[u] = ((u64)(u32)g.Bcol[pp[u]] << 32) | (u32)sl;
+            kc[u] = g.Bcol[pp[u]];
             x[u] = g.Bval[pp[u]];
         }
     }
 #pragma unroll
+    for (int u = 0; u < U; ++u) x[u] *= ra[u];
+#pragma unroll
     for (int u = 0; u < U; ++u) {
-        const u32 khi = (u32)(key[u] >> 32), klo = (u32)key[u];
+        const u32 khi = (u32)kc[u], klo = sl < P[u] ? (u32)sl : ~0u;
+        const u64 key = ((u64)khi << 32) | klo;
+        // the group's column span [clo, chi] (chi - clo < 0: no products)
+        const bool has = sl < P[u];
+        int clo = has ? (int)khi : INT_MAX, chi = has ? (int)khi : 0;
+        if constexpr (G == 64) {
+            clo = wave_last(wave_incl_dpp(clo, INT_MAX, OpMin{}));
+            chi = wave_last(wave_incl_dpp(chi, 0, OpMax{}));
+        } else {
+            clo = min(clo, dpp_mov<0x111, 0xf>(INT_MAX, clo));  // row_shr:1, 2, 4, 8
+            clo = min(clo, dpp_mov<0x112, 0xf>(INT_MAX, clo));
+            clo = min(clo, dpp_mov<0x114, 0xf>(INT_MAX, clo));
+            clo = row_bcast16<15>(min(clo, dpp_mov<0x118, 0xf>(INT_MAX, clo)));
+            chi = max(chi, dpp_mov<0x111, 0xf>(0, chi));
+            chi = max(chi, dpp_mov<0x112, 0xf>(0, chi));
+            chi = max(chi, dpp_mov<0x114, 0xf>(0, chi));
+            chi = row_bcast16<15>(max(chi, dpp_mov<0x118, 0xf>(0, chi)));
+        }
+        // (strict: the largest packed key stays below the ~0u padding; wave-uniform:
+        // S64's span is the wave's, S16's four rows pack together or not at all)
+        bool packed = chi - clo < (1 << (32 - SK_LB)) - 1;
+        if constexpr (G < 64) packed = __all(packed);
+        if (packed) {
+            // the keys are unique and ties on the column keep lane order: the
+            // same order, hence the same sums, as the counted ranks below
+            u32 kx = has ? ((u32)((int)khi - clo) << SK_LB) | (u32)sl : ~0u;
+            group_sort<G>(kx, sl);
+            // position sl: its column and the lane its product came from
+            const int src = (int)(kx & (u32)(G - 1));
+            const double pv = __shfl(x[u], src, G);
+            if (has) {
+                sk[wv][u][gb + sl] = ((u64)(u32)((int)(kx >> SK_LB) + clo) << 32) | (u32)src;
+                sv[wv][u][gb + sl] = pv;
+            }
+            continue;
+        }
         int rank = 0;
         if constexpr (G == 64) {  // one row per wave: P is wave-uniform, scalar reads of each key
             for (int f = 0; f < P[u]; ++f) {
                 const u64 kf = ((u64)(u32)__builtin_amdgcn_readlane((int)khi, f) << 32) |
                                (u32)__builtin_amdgcn_readlane((int)klo, f);
-                rank += kf < key[u];
+                rank += kf < key;
             }
         } else {
-            const u64 ku = key[u];
+            const u64 ku = key;
             static_for<0, 16>([&](auto fc) {
                 constexpr int f = decltype(fc)::value;
                 const u64 kf = ((u64)(u32)row_bcast16<f>((int)khi) << 32) | (u32)row_bcast16<f>((int)klo);
@@ -459,9 +537,14 @@ __global__ __launch_bounds__(WG) void k_rows_small(RowsArgs g) {
             });
         }
         if (sl < P[u]) {
-            sk[wv][u][gb + rank] = key[u];
-            sv[wv][u][gb + rank] = ra[u] * x[u];
+            sk[wv][u][gb + rank] = key;
+            sv[wv][u][gb + rank] = x[u];
         }
+    }
+    if constexpr (G < 64) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (live[u]) base[u] = g.E[a0[u]];
     }
     wave_lds_sync();
     const u64 gm = (G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull)) << gb;
@@ -505,22 +588,6 @@ __device__ __forceinline__ void search_ilp(const T *a, int (&b)[U], int (&len)[U
         }
     }
 }
-
-// lane l's value of lane l ^ D (D a power of two below 64): DPP quad
-// permutes for 1 and 2, ds_swizzle's xor mode inside 32 lanes, ds_bpermute for 32
-template <int D> __device__ __forceinline__ u32 lane_xor(u32 v) {
-    if constexpr (D == 1) return (u32)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xf, 0xf, false);  // [1,0,3,2]
-    else if constexpr (D == 2) return (u32)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xf, 0xf, false);  // [2,3,0,1]
-    else if constexpr (D < 32) return (u32)__builtin_amdgcn_ds_swizzle((int)v, (D << 10) | 0x1f);
-    else return (u32)__shfl_xor((int)v, D, 64);
-}
-
-// med3(a, b, 0) = min(a, b) and med3(a, b, ~0u) = max(a, b): a compare-exchange
-// side picked by a selector (per lane or wave-uniform) is one v_med3_u32
-__device__ __forceinline__ u32 minmax_sel(u32 a, u32 b, u32 sel) { return min(max(a, b), max(min(a, b), sel)); }
-// bit B of v spread over the word: 0 or ~0u (one v_bfe_i32)
-template <int B> __device__ __forceinline__ u32 bit_fill(u32 v) { return (u32)((int)(v << (31 - B)) >> 31); }
-constexpr int ilog2_c(int v) { return v <= 1 ? 0 : 1 + ilog2_c(v >> 1); }
 
 // one bitonic stage at element distance J inside sequences of K (elements
 // e = 4*lane + u): ascending where e & K == 0

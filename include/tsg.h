@@ -186,6 +186,53 @@ int tsg_spgemm_csr_masked(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatri
  * C->columnindex too).  stats may be NULL. */
 int tsg_spgemm_csr_symbolic(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, int mode, tsg_stats *stats);
 
+/* ---- semirings of the numeric and masked plans ----
+ * c(i,j) = (+) over the k with A(i,k) and B(k,j) both stored of A(i,k) (x)
+ * B(k,j), for a semiring ((+), (x)) chosen per run (a plan holds patterns only:
+ * one plan serves every semiring).
+ *  - Entries are structural: a stored 0.0 takes part (in MIN_PLUS it is a
+ *    zero-length edge), and no result is dropped, so C's pattern is the same
+ *    for every semiring: tsg_dev_spgemm_symbolic's.
+ *  - A pattern or mask entry no product reaches gets the (+)-identity: +inf for
+ *    MIN_*, -inf for MAX_*, 0.0 for PLUS_* (also in a row whose A row is empty).
+ *  - A column repeated in a B row is combined with (+) on the row-wise leg, as
+ *    it is added by the arithmetic product.
+ *  - NaN inputs and the sign of a zero result are unspecified for the min / max
+ *    semirings.
+ *  - For the five min / max semirings and PLUS_PAIR the result does not depend
+ *    on the order of the sum: both legs of the masked plan and every class of
+ *    the numeric plan are bit-reproducible, and agree with each other bit for
+ *    bit.  (PLUS_TIMES: the dot leg only, as before.) */
+#define TSG_SEMIRING_PLUS_TIMES 0  /* the arithmetic product: what every other call computes */
+#define TSG_SEMIRING_MIN_PLUS   1  /* identity +inf */
+#define TSG_SEMIRING_MAX_PLUS   2  /* identity -inf */
+#define TSG_SEMIRING_MAX_TIMES  3  /* identity -inf */
+#define TSG_SEMIRING_MAX_MIN    4  /* identity -inf */
+#define TSG_SEMIRING_MIN_MAX    5  /* identity +inf */
+#define TSG_SEMIRING_PLUS_PAIR  6  /* every product counts 1.0; a_val / b_val are not read and may be NULL; identity 0 */
+
+/* *identity := the semiring's (+)-identity.  Host only (no device is touched);
+ * TSG_ERR_INVALID for an unknown semiring or a NULL identity. */
+int tsg_semiring_identity(int semiring, double *identity);
+/* "plus_times", "min_plus", "max_plus", "max_times", "max_min", "min_max",
+ * "plus_pair"; NULL for an unknown semiring. */
+const char *tsg_semiring_name(int semiring);
+
+/* One shot host CSR -> host CSR over a semiring: C = A (+).(x) B on A*B's full
+ * structural pattern.  Uploads A and B, runs the symbolic pass, creates a
+ * numeric plan on its pattern, runs it once with the semiring and destroys it,
+ * downloads C.  C->rowpointer / columnindex / value are malloc'd like
+ * tsg_spgemm_csr's.  PLUS_PAIR: A->value / B->value are not read and may be
+ * NULL.  TSG_ERR_INVALID for an unknown semiring (nothing is launched).
+ * stats (nullable): the numeric run's. */
+int tsg_spgemm_csr_semiring(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, int semiring,
+                            tsg_stats *stats);
+/* tsg_spgemm_csr_masked over a semiring: C->value[p] := the (+)-sum of the
+ * products reaching mask entry p, the (+)-identity where none does.
+ * TSG_SEMIRING_PLUS_TIMES is tsg_spgemm_csr_masked itself. */
+int tsg_spgemm_csr_masked_semiring(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, int mode, int semiring,
+                                   tsg_stats *stats);
+
 /* Frees every non-NULL pointer field and zeroes the struct (covers the
  * reference's matrix_destroy, src/csr2tile.h:509-518, and the CSR arrays). */
 void tsg_matrix_destroy(tsg_smatrix *M);
@@ -324,6 +371,15 @@ int tsg_dev_numeric_plan_create(tsg_context *ctx, const tsg_dev_csr *A, const ts
  * (= products), nnzC, path = TSG_PATH_NUMERIC; the rest 0 or -1. */
 int tsg_dev_numeric_run(tsg_context *ctx, tsg_numeric_plan *plan, const double *a_val,
                         const double *b_val, double *c_val, void *stream, tsg_stats *stats /*nullable*/);
+/* tsg_dev_numeric_run over a semiring (TSG_SEMIRING_*, above): c_val[p] := the
+ * (+)-sum of the products reaching pattern entry p, the (+)-identity where none
+ * does.  An unknown semiring returns TSG_ERR_INVALID before anything is
+ * launched (c_val untouched).  A product on a column the pattern lacks returns
+ * TSG_ERR_INVALID as above, for every semiring.  TSG_SEMIRING_PLUS_PAIR reads
+ * neither a_val nor b_val (they may be NULL).  TSG_SEMIRING_PLUS_TIMES is
+ * tsg_dev_numeric_run itself.  stats as there (path = TSG_PATH_NUMERIC). */
+int tsg_dev_numeric_run_semiring(tsg_context *ctx, tsg_numeric_plan *plan, int semiring, const double *a_val,
+                                 const double *b_val, double *c_val, void *stream, tsg_stats *stats /*nullable*/);
 /* TSG_ERR_INVALID for a plan that is not alive on ctx (e.g. destroyed twice). */
 int tsg_dev_numeric_plan_destroy(tsg_context *ctx, tsg_numeric_plan *plan);
 
@@ -379,6 +435,16 @@ int tsg_dev_masked_plan_create(tsg_context *ctx, const tsg_dev_csr *A, const tsg
  * the rest as in the numeric run. */
 int tsg_dev_masked_run(tsg_context *ctx, tsg_masked_plan *plan, const double *a_val, const double *b_val,
                        double *c_val, void *stream, tsg_stats *stats /*nullable*/);
+/* tsg_dev_masked_run over a semiring (TSG_SEMIRING_*, above): c_val[p] := the
+ * (+)-sum over k of A(i,k) (x) B(k,j) for every mask entry p = (i, j), the
+ * (+)-identity where no product reaches (a mask entry on an empty A row
+ * included); products elsewhere are dropped.  An unknown semiring returns
+ * TSG_ERR_INVALID before anything is launched (c_val untouched).
+ * TSG_SEMIRING_PLUS_PAIR reads neither a_val nor b_val (they may be NULL) and
+ * skips the gather of b_val into B^T's order.  TSG_SEMIRING_PLUS_TIMES is
+ * tsg_dev_masked_run itself.  stats as there (path = TSG_PATH_MASKED). */
+int tsg_dev_masked_run_semiring(tsg_context *ctx, tsg_masked_plan *plan, int semiring, const double *a_val,
+                                const double *b_val, double *c_val, void *stream, tsg_stats *stats /*nullable*/);
 /* TSG_ERR_INVALID for a plan that is not alive on ctx (e.g. destroyed twice). */
 int tsg_dev_masked_plan_destroy(tsg_context *ctx, tsg_masked_plan *plan);
 

@@ -133,6 +133,12 @@ _SIGS = {
                                C.POINTER(Stats)], C.c_int),
     "tsg_spgemm_csr_symbolic": ([C.POINTER(SMatrix), C.POINTER(SMatrix), C.POINTER(SMatrix), C.c_int,
                                  C.POINTER(Stats)], C.c_int),
+    "tsg_semiring_identity": ([C.c_int, C.POINTER(C.c_double)], C.c_int),
+    "tsg_semiring_name": ([C.c_int], C.c_char_p),
+    "tsg_spgemm_csr_semiring": ([C.POINTER(SMatrix), C.POINTER(SMatrix), C.POINTER(SMatrix), C.c_int,
+                                 C.POINTER(Stats)], C.c_int),
+    "tsg_spgemm_csr_masked_semiring": ([C.POINTER(SMatrix), C.POINTER(SMatrix), C.POINTER(SMatrix), C.c_int, C.c_int,
+                                        C.POINTER(Stats)], C.c_int),
     "tsg_matrix_destroy": ([C.POINTER(SMatrix)], None),
     "tsg_context_create": ([C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "tsg_context_destroy": ([C.c_void_p], C.c_int),
@@ -156,11 +162,15 @@ _SIGS = {
                                      C.POINTER(C.c_void_p), C.POINTER(NumericInfo)], C.c_int),
     "tsg_dev_numeric_run": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                              C.POINTER(Stats)], C.c_int),
+    "tsg_dev_numeric_run_semiring": ([C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(Stats)], C.c_int),
     "tsg_dev_numeric_plan_destroy": ([C.c_void_p, C.c_void_p], C.c_int),
     "tsg_dev_masked_plan_create": ([C.c_void_p, C.POINTER(DevCSR), C.POINTER(DevCSR), C.POINTER(DevCSR), C.c_int,
                                     C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(MaskedInfo)], C.c_int),
     "tsg_dev_masked_run": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.POINTER(Stats)], C.c_int),
+    "tsg_dev_masked_run_semiring": ([C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(Stats)], C.c_int),
     "tsg_dev_masked_plan_destroy": ([C.c_void_p, C.c_void_p], C.c_int),
     "tsg_dev_spgemm_symbolic": ([C.c_void_p, C.POINTER(DevCSR), C.POINTER(DevCSR), C.c_int, C.c_void_p,
                                  C.POINTER(DevCSR), C.POINTER(SymbolicInfo), C.POINTER(Stats)], C.c_int),

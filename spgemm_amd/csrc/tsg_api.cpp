@@ -1321,16 +1321,39 @@ int tsg_dev_numeric_plan_create(tsg_context *ctx, const tsg_dev_csr *A, const ts
     return TSG_OK;
 }
 
+// ---- semirings (tsg_semiring.h has the kernels' traits)
+int tsg_semiring_identity(int semiring, double *identity) {
+    if (!identity) return TSG_ERR_INVALID;
+    return semiring_identity(semiring, identity);
+}
+
+const char *tsg_semiring_name(int semiring) {
+    static const char *const names[] = {"plus_times", "min_plus", "max_plus", "max_times",
+                                        "max_min",    "min_max",  "plus_pair"};
+    return semiring_known(semiring) ? names[semiring] : nullptr;
+}
+
+// whether the semiring reads a_val / b_val (PLUS_PAIR does not: they may be NULL)
+static bool semiring_reads_values(int semiring) { return semiring != TSG_SEMIRING_PLUS_PAIR; }
+
 int tsg_dev_numeric_run(tsg_context *ctx, tsg_numeric_plan *plan, const double *a_val, const double *b_val,
                         double *c_val, void *stream, tsg_stats *stats) {
+    return tsg_dev_numeric_run_semiring(ctx, plan, TSG_SEMIRING_PLUS_TIMES, a_val, b_val, c_val, stream, stats);
+}
+
+int tsg_dev_numeric_run_semiring(tsg_context *ctx, tsg_numeric_plan *plan, int semiring, const double *a_val,
+                                 const double *b_val, double *c_val, void *stream, tsg_stats *stats) {
     if (!ctx || !plan || std::find(ctx->plans.begin(), ctx->plans.end(), plan) == ctx->plans.end())
         return TSG_ERR_INVALID;
+    if (!semiring_known(semiring)) return TSG_ERR_INVALID;  // (before anything is launched)
     NumericPlan &p = plan->p;
-    if ((p.A.nnz && !a_val) || (p.B.nnz && !b_val) || (p.C.nnz && !c_val)) return TSG_ERR_INVALID;
+    const bool vals = semiring_reads_values(semiring);
+    if ((vals && p.A.nnz && !a_val) || (vals && p.B.nnz && !b_val) || (p.C.nnz && !c_val)) return TSG_ERR_INVALID;
     Context &cx = ctx->cx;
     auto h0 = std::chrono::steady_clock::now();
     int missed = 0;
-    TSG_TRY(dev_numeric_run(cx, p, a_val, b_val, c_val, (hipStream_t)stream, stats ? cx.ev : nullptr, &missed));
+    TSG_TRY(dev_numeric_run(cx, p, semiring, a_val, b_val, c_val, (hipStream_t)stream, stats ? cx.ev : nullptr,
+                            &missed));
     if (stats) {
         auto h1 = std::chrono::steady_clock::now();
         tsg_stats st{};
@@ -1465,14 +1488,21 @@ int tsg_dev_masked_plan_create(tsg_context *ctx, const tsg_dev_csr *A, const tsg
 
 int tsg_dev_masked_run(tsg_context *ctx, tsg_masked_plan *plan, const double *a_val, const double *b_val,
                        double *c_val, void *stream, tsg_stats *stats) {
+    return tsg_dev_masked_run_semiring(ctx, plan, TSG_SEMIRING_PLUS_TIMES, a_val, b_val, c_val, stream, stats);
+}
+
+int tsg_dev_masked_run_semiring(tsg_context *ctx, tsg_masked_plan *plan, int semiring, const double *a_val,
+                                const double *b_val, double *c_val, void *stream, tsg_stats *stats) {
     if (!ctx || !plan ||
         std::find(ctx->masked_plans.begin(), ctx->masked_plans.end(), plan) == ctx->masked_plans.end())
         return TSG_ERR_INVALID;
+    if (!semiring_known(semiring)) return TSG_ERR_INVALID;  // (before anything is launched)
     MaskedPlan &p = plan->p;
-    if ((p.A.nnz && !a_val) || (p.B.nnz && !b_val) || (p.M.nnz && !c_val)) return TSG_ERR_INVALID;
+    const bool vals = semiring_reads_values(semiring);
+    if ((vals && p.A.nnz && !a_val) || (vals && p.B.nnz && !b_val) || (p.M.nnz && !c_val)) return TSG_ERR_INVALID;
     Context &cx = ctx->cx;
     auto h0 = std::chrono::steady_clock::now();
-    TSG_TRY(dev_masked_run(cx, p, a_val, b_val, c_val, (hipStream_t)stream, stats ? cx.ev : nullptr));
+    TSG_TRY(dev_masked_run(cx, p, semiring, a_val, b_val, c_val, (hipStream_t)stream, stats ? cx.ev : nullptr));
     if (stats) {
         auto h1 = std::chrono::steady_clock::now();
         tsg_stats st{};
@@ -1498,20 +1528,36 @@ int tsg_dev_masked_plan_destroy(tsg_context *ctx, tsg_masked_plan *plan) {
 }
 
 int tsg_spgemm_csr_masked(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, int mode, tsg_stats *stats) {
+    return tsg_spgemm_csr_masked_semiring(A, B, C, mode, TSG_SEMIRING_PLUS_TIMES, stats);
+}
+
+// a host operand of a semiring call: well-formed, values present where the semiring reads them
+static bool host_operand_ok(const tsg_smatrix *M, bool vals) {
+    return M->nnz >= 0 && M->m >= 0 && M->rowpointer && (!M->nnz || (M->columnindex && (M->value || !vals)));
+}
+
+// upload_csr for an operand whose values the semiring may not read (then value stays null)
+static int upload_operand(PoolScope &ws, const tsg_smatrix *M, bool vals, tsg_dev_csr &d, hipStream_t s) {
+    if (vals) return upload_csr(ws, M, d, s);
+    d = tsg_dev_csr{M->m, M->n, M->nnz, nullptr, nullptr, nullptr};
+    TSG_TRY(upload(ws, &d.rowpointer, M->rowpointer, (size_t)M->m + 1, s));
+    return upload(ws, &d.columnindex, M->columnindex, (size_t)M->nnz, s);
+}
+
+int tsg_spgemm_csr_masked_semiring(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, int mode, int semiring,
+                                   tsg_stats *stats) {
     if (!A || !B || !C || A->n != B->m || C->m != A->m || C->n != B->n) return TSG_ERR_INVALID;
-    if (A->nnz < 0 || B->nnz < 0 || C->nnz < 0 || A->m < 0 || B->m < 0) return TSG_ERR_INVALID;
-    if (!A->rowpointer || !B->rowpointer || !C->rowpointer) return TSG_ERR_INVALID;
-    if ((A->nnz && (!A->columnindex || !A->value)) || (B->nnz && (!B->columnindex || !B->value)) ||
-        (C->nnz && (!C->columnindex || !C->value)))
-        return TSG_ERR_INVALID;
+    if (!semiring_known(semiring)) return TSG_ERR_INVALID;
+    const bool vals = semiring_reads_values(semiring);
+    if (!host_operand_ok(A, vals) || !host_operand_ok(B, vals) || !host_operand_ok(C, true)) return TSG_ERR_INVALID;
     HostLease lease;
     TSG_TRY(lease.acquire());
     Context &cx = lease.cx();
     hipStream_t s = lease.stream();
     PoolScope ws(cx);  // (the uploads; what the dev_* calls keep returns with the lease)
     tsg_dev_csr dA, dB, dC;
-    int rc = upload_csr(ws, A, dA, s);
-    if (rc == TSG_OK) rc = upload_csr(ws, B, dB, s);
+    int rc = upload_operand(ws, A, vals, dA, s);
+    if (rc == TSG_OK) rc = upload_operand(ws, B, vals, dB, s);
     if (rc == TSG_OK) {
         dC.m = C->m; dC.n = C->n; dC.nnz = C->nnz;
         rc = upload(ws, &dC.rowpointer, C->rowpointer, (size_t)C->m + 1, s);
@@ -1522,7 +1568,7 @@ int tsg_spgemm_csr_masked(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatri
     tsg_masked_plan *plan = nullptr;
     if (rc == TSG_OK) rc = tsg_dev_masked_plan_create(lease.ctx(), &dA, &dB, &dC, mode, s, &plan, nullptr);
     if (rc == TSG_OK) {
-        rc = tsg_dev_masked_run(lease.ctx(), plan, dA.value, dB.value, dC.value, s, stats);
+        rc = tsg_dev_masked_run_semiring(lease.ctx(), plan, semiring, dA.value, dB.value, dC.value, s, stats);
         if (rc == TSG_OK && C->nnz) {
             if (hipMemcpyAsync(C->value, dC.value, (size_t)C->nnz * sizeof(double), hipMemcpyDeviceToHost, s) !=
                     hipSuccess ||
@@ -1530,6 +1576,39 @@ int tsg_spgemm_csr_masked(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatri
                 rc = TSG_ERR_HIP;
         }
         (void)tsg_dev_masked_plan_destroy(lease.ctx(), plan);
+    }
+    return rc;
+}
+
+// ---- the full product over a semiring: symbolic pass, numeric plan, one run
+int tsg_spgemm_csr_semiring(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, int semiring,
+                            tsg_stats *stats) {
+    if (!A || !B || !C || A->n != B->m) return TSG_ERR_INVALID;
+    if (!semiring_known(semiring)) return TSG_ERR_INVALID;
+    const bool vals = semiring_reads_values(semiring);
+    if (!host_operand_ok(A, vals) || !host_operand_ok(B, vals)) return TSG_ERR_INVALID;
+    HostLease lease;
+    TSG_TRY(lease.acquire());
+    Context &cx = lease.cx();
+    hipStream_t s = lease.stream();
+    PoolScope ws(cx);  // (the uploads and C's values; what the dev_* calls keep returns with the lease)
+    tsg_dev_csr dA, dB, dC{};
+    TSG_TRY(upload_operand(ws, A, vals, dA, s));
+    TSG_TRY(upload_operand(ws, B, vals, dB, s));
+    TSG_HIP(hipStreamSynchronize(s));
+    TSG_TRY(tsg_dev_spgemm_symbolic(lease.ctx(), &dA, &dB, TSG_SYMBOLIC_PATTERN, s, &dC, nullptr, nullptr));
+    TSG_TRY(ws.get(&dC.value, (size_t)dC.nnz + 1));
+    tsg_numeric_plan *plan = nullptr;
+    TSG_TRY(tsg_dev_numeric_plan_create(lease.ctx(), &dA, &dB, &dC, s, &plan, nullptr));
+    int rc = tsg_dev_numeric_run_semiring(lease.ctx(), plan, semiring, dA.value, dB.value, dC.value, s, stats);
+    (void)tsg_dev_numeric_plan_destroy(lease.ctx(), plan);
+    if (rc == TSG_OK) {
+        memset(C, 0, sizeof(*C));
+        C->m = dC.m; C->n = dC.n; C->nnz = dC.nnz;
+        rc = download(&C->rowpointer, dC.rowpointer, (size_t)dC.m + 1, s);
+        if (rc == TSG_OK) rc = download(&C->columnindex, dC.columnindex, (size_t)dC.nnz, s);
+        if (rc == TSG_OK) rc = download(&C->value, dC.value, (size_t)dC.nnz, s);
+        if (rc == TSG_OK && hipStreamSynchronize(s) != hipSuccess) rc = TSG_ERR_HIP;
     }
     return rc;
 }

@@ -447,8 +447,12 @@ int dev_operands_validate(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &
 int dev_numeric_plan_create(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &Cp,
                             NumericPlan &p, hipStream_t s, const unsigned char *skip = nullptr,
                             const bool *validated = nullptr);
-int dev_numeric_run(Context &cx, NumericPlan &p, const double *a_val, const double *b_val, double *c_val,
-                    hipStream_t s, hipEvent_t *ev, int *missed);
+// semiring: a TSG_SEMIRING_* value (tsg_semiring.h has the traits the kernels
+// are instantiated on); an unknown one returns TSG_ERR_INVALID with nothing queued
+bool semiring_known(int semiring);
+int semiring_identity(int semiring, double *identity);  // (host code: the traits' identity, no device touched)
+int dev_numeric_run(Context &cx, NumericPlan &p, int semiring, const double *a_val, const double *b_val,
+                    double *c_val, hipStream_t s, hipEvent_t *ev, int *missed);
 void dev_numeric_plan_free(NumericPlan &p);
 
 // masked product C<M> = A*B on the mask's pattern only (tsg_masked.hip,
@@ -479,8 +483,8 @@ struct MaskedPlan {
 int dev_masked_plan_create(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &M, int mode,
                            MaskedPlan &p, hipStream_t s);
 // ev (optional): ev[6] before the first kernel, ev[5] after the last
-int dev_masked_run(Context &cx, MaskedPlan &p, const double *a_val, const double *b_val, double *c_val,
-                   hipStream_t s, hipEvent_t *ev);
+int dev_masked_run(Context &cx, MaskedPlan &p, int semiring, const double *a_val, const double *b_val,
+                   double *c_val, hipStream_t s, hipEvent_t *ev);
 void dev_masked_plan_free(MaskedPlan &p);
 
 // symbolic product (tsg_symbolic.hip): C's row pointers

@@ -29,10 +29,16 @@
 // shorter list's entries l, l + 16, ... in turn, then the lanes' sums are added
 // in a fixed tree), so its values are bit-reproducible from run to run.  The
 // two legs write disjoint rows.  DESIGN.md section 3.8.
+//
+// The arithmetic is a semiring's (tsg_semiring.h): the
+// dot kernel is templated on its traits -- "multiply" above is mul, "sum" its
+// (+) from its identity, which is also what an entry no product reaches holds
+// -- and dev_masked_run picks the instantiation of both legs.
 #include <algorithm>
 #include <vector>
 
 #include "tsg_dev_common.h"
+#include "tsg_semiring.h"
 
 namespace tsg {
 
@@ -149,31 +155,41 @@ struct MskOps {
 constexpr int MSK_G = 16;   // lanes per mask entry: one DPP row
 constexpr int MSK_ILP = 4;  // searches per lane in flight
 
-// inclusive sum over a 16-lane DPP row (for_products' row steps, on both halves
-// of the double): the row's last lane ends with the sum of all 16, always added
-// in the same order.  The row is wholly active or not at all.
-template <int CTRL> __device__ __forceinline__ double row_shr_add(double x) {
-    const int lo = dpp_mov<CTRL, 0xf>(0, __double2loint(x)), hi = dpp_mov<CTRL, 0xf>(0, __double2hiint(x));
-    return x + __hiloint2double(hi, lo);  // (a lane without a source adds 0.0)
+// inclusive (+)-sum over a 16-lane DPP row (for_products' row steps, on both
+// halves of the double): the row's last lane ends with the sum of all 16, always
+// combined in the same order.  The row is wholly active or not at all.  A lane
+// without a source takes the DPP move's old value: the bits of the semiring's
+// identity (all zero for +; a zero there would win a min over positive values
+// or a max over negative ones in lane 0 at the first step and reach lane 15,
+// the lane that stores, by the last).
+template <class SR, int CTRL> __device__ __forceinline__ double row_shr_comb(double x) {
+    const double id = SR::identity();
+    const int lo = dpp_mov<CTRL, 0xf>(__double2loint(id), __double2loint(x)),
+              hi = dpp_mov<CTRL, 0xf>(__double2hiint(id), __double2hiint(x));
+    return SR::add(x, __hiloint2double(hi, lo));
 }
-__device__ __forceinline__ double row16_incl_sum(double x) {
-    x = row_shr_add<0x111>(x);  // row_shr:1
-    x = row_shr_add<0x112>(x);  // row_shr:2
-    x = row_shr_add<0x114>(x);  // row_shr:4
-    x = row_shr_add<0x118>(x);  // row_shr:8
+template <class SR> __device__ __forceinline__ double row16_incl_sum(double x) {
+    x = row_shr_comb<SR, 0x111>(x);  // row_shr:1
+    x = row_shr_comb<SR, 0x112>(x);  // row_shr:2
+    x = row_shr_comb<SR, 0x114>(x);  // row_shr:4
+    x = row_shr_comb<SR, 0x118>(x);  // row_shr:8
     return x;
 }
 
-// Lane l's share of sum over the columns common to a short list (ks, vs: ns
-// entries) and a long one (kl, vl: nl >= ns entries, strictly ascending).  The
+// Lane l's share of the (+)-sum over the columns common to a short list (ks, vs:
+// ns entries) and a long one (kl, vl: nl >= ns entries, strictly ascending),
+// from the semiring's identity.  The
 // group strides the short list MSK_ILP * 16 entries at a time; each key is
 // searched in the long list by a bounded branchless search whose trip count
 // depends on nl alone (uniform over the group: the MSK_ILP searches interleave)
 // and whose every read lies in [0, nl).  A lane past the short list's end
-// searches INT_MAX, which no column equals.
+// searches INT_MAX, which no column equals.  A semiring that reads no values
+// touches neither vs nor vl.  (Every (x) here commutes: which list is A's does
+// not matter.)
+template <class SR>
 __device__ __forceinline__ double msk_intersect(const int *ks, const double *vs, int ns, const int *kl,
                                                 const double *vl, int nl, int l) {
-    double acc = 0.0;
+    double acc = SR::identity();
     for (int b = 0; b < ns; b += MSK_ILP * MSK_G) {  // (ns > 0 here, so nl > 0)
         int k[MSK_ILP], key[MSK_ILP], base[MSK_ILP];
 #pragma unroll
@@ -191,14 +207,16 @@ __device__ __forceinline__ double msk_intersect(const int *ks, const double *vs,
         }
 #pragma unroll
         for (int u = 0; u < MSK_ILP; ++u)
-            if (kl[base[u]] == key[u]) acc += vs[k[u]] * vl[base[u]];
+            if (kl[base[u]] == key[u]) acc = SR::add(acc, SR::mul(sr_load<SR>(vs, k[u]), sr_load<SR>(vl, base[u])));
     }
     return acc;
 }
 
 // one dot unit per workgroup: (row, first mask entry, entries, -).  The 16
 // groups of 16 lanes take the unit's mask entries round-robin; the group's last
-// lane stores the entry's value once.
+// lane stores the entry's value once (the identity where the lists share no
+// column, an empty A row included).
+template <class SR>
 __global__ __launch_bounds__(WG) void k_msk_dot(const int4 *units, MskOps o) {
     __shared__ int s_col[kMskRowLds];
     __shared__ double s_val[kMskRowLds];
@@ -208,7 +226,7 @@ __global__ __launch_bounds__(WG) void k_msk_dot(const int4 *units, MskOps o) {
     if (lds) {
         for (int q = threadIdx.x; q < la; q += WG) {
             s_col[q] = o.ciA[a0 + q];
-            s_val[q] = o.a_val[a0 + q];
+            if constexpr (SR::kValues) s_val[q] = o.a_val[a0 + q];
         }
         __syncthreads();
     }
@@ -221,11 +239,12 @@ __global__ __launch_bounds__(WG) void k_msk_dot(const int4 *units, MskOps o) {
         const double *vt = o.t_val + t0;
         double acc;
         if (lds)
-            acc = la <= lt ? msk_intersect(s_col, s_val, la, ct, vt, lt, l) : msk_intersect(ct, vt, lt, s_col, s_val, la, l);
+            acc = la <= lt ? msk_intersect<SR>(s_col, s_val, la, ct, vt, lt, l)
+                           : msk_intersect<SR>(ct, vt, lt, s_col, s_val, la, l);
         else
-            acc = la <= lt ? msk_intersect(o.ciA + a0, o.a_val + a0, la, ct, vt, lt, l)
-                           : msk_intersect(ct, vt, lt, o.ciA + a0, o.a_val + a0, la, l);
-        acc = row16_incl_sum(acc);
+            acc = la <= lt ? msk_intersect<SR>(o.ciA + a0, o.a_val + a0, la, ct, vt, lt, l)
+                           : msk_intersect<SR>(ct, vt, lt, o.ciA + a0, o.a_val + a0, la, l);
+        acc = row16_incl_sum<SR>(acc);
         if (l == MSK_G - 1) o.c_val[p] = acc;
     }
 }
@@ -393,20 +412,28 @@ int dev_masked_plan_create(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr 
 
 // Queued on s and waited for: no allocation, every geometry from the plan.  The
 // dot units first (the longest-running workgroups), then the row-wise leg in
-// dev_numeric_run's order, which also waits for the stream.
-int dev_masked_run(Context &cx, MaskedPlan &p, const double *a_val, const double *b_val, double *c_val,
-                   hipStream_t s, hipEvent_t *ev) {
+// dev_numeric_run's order, which also waits for the stream.  The semiring picks
+// both legs' instantiations (tsg_semiring.h); one that reads no values skips the
+// gather.  An unknown semiring: TSG_ERR_INVALID, nothing queued.
+int dev_masked_run(Context &cx, MaskedPlan &p, int semiring, const double *a_val, const double *b_val,
+                   double *c_val, hipStream_t s, hipEvent_t *ev) {
+    if (!semiring_known(semiring)) return TSG_ERR_INVALID;
     if (ev) TSG_HIP(hipEventRecord(ev[6], s));
     if (p.nunits) {
-        if (p.B.nnz) k_msk_gather<<<grid_for(p.B.nnz, WG * 4, 8192), WG, 0, s>>>(p.bt_pos, p.B.nnz, b_val, p.bt_val);
         const MskOps o{p.A.rowpointer, p.A.columnindex, p.M.rowpointer, p.M.columnindex, p.bt_rp, p.bt_ci,
                        a_val,          p.bt_val,        c_val};
-        for (int u0 = 0; u0 < p.nunits; u0 += kMaxGridBlocks)  // (a grid holds fewer than 2^32 threads)
-            k_msk_dot<<<std::min(p.nunits - u0, kMaxGridBlocks), WG, 0, s>>>(p.units + u0, o);
+        (void)semiring_dispatch(semiring, [&](auto sr) {
+            using SR = decltype(sr);
+            if (SR::kValues && p.B.nnz)
+                k_msk_gather<<<grid_for(p.B.nnz, WG * 4, 8192), WG, 0, s>>>(p.bt_pos, p.B.nnz, b_val, p.bt_val);
+            for (int u0 = 0; u0 < p.nunits; u0 += kMaxGridBlocks)  // (a grid holds fewer than 2^32 threads)
+                k_msk_dot<SR><<<std::min(p.nunits - u0, kMaxGridBlocks), WG, 0, s>>>(p.units + u0, o);
+            return TSG_OK;
+        });
         TSG_HIP(hipGetLastError());
     }
     int missed = 0;  // (products whose column the mask lacks: dropped, by definition)
-    return dev_numeric_run(cx, p.rows, a_val, b_val, c_val, s, ev, &missed);
+    return dev_numeric_run(cx, p.rows, semiring, a_val, b_val, c_val, s, ev, &missed);
 }
 
 }  // namespace tsg

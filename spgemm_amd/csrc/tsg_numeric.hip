@@ -26,10 +26,16 @@
 // repeat a column: all sums are atomic adds (LDS: ds_add_f64; global: the plain
 // atomicAdd(double *), correct on fine-grained memory too -- c_val is the
 // caller's, its kind unknown).  DESIGN.md section 3.7 has the measurements.
+//
+// The arithmetic is a semiring's (tsg_semiring.h): the
+// run-time kernels are templated on its traits -- "a*b" above is mul, "added"
+// the semiring's atomic (+), "zeroes" a fill with its identity -- and
+// dev_numeric_run picks the instantiation; the plan knows nothing of it.
 #include <algorithm>
 #include <vector>
 
 #include "tsg_dev_common.h"
+#include "tsg_semiring.h"
 
 namespace tsg {
 
@@ -117,8 +123,9 @@ __device__ __forceinline__ int owner_search_u(const int *off, int n, int it) {
 }
 
 // add(q, a, commit): the product of B entry q with the A value a; everything up
-// to the sum itself runs for commit == false too (q is then some valid entry)
-template <int T, class F>
+// to the sum itself runs for commit == false too (q is then some valid entry).
+// A semiring that reads no values (SR::kValues false) loads no a_val: a is 1.0.
+template <int T, class SR, class F>
 __device__ __forceinline__ void for_products(const NumOps &o, int e0, int e1, int t, int *s_off, int *s_bs,
                                              double *s_a, int *red, F add) {
     for (int eb = e0; eb < e1; eb += T) {
@@ -129,7 +136,7 @@ __device__ __forceinline__ void for_products(const NumOps &o, int e0, int e1, in
             const int k = o.ciA[e];
             bs = o.rpB[k];
             bl = o.rpB[k + 1] - bs;
-            a = o.a_val[e];
+            a = sr_load<SR>(o.a_val, e);
         }
         const int nv = min(T, e1 - eb);
         int total, off;
@@ -152,14 +159,14 @@ __device__ __forceinline__ void for_products(const NumOps &o, int e0, int e1, in
         }
         s_off[t] = off;
         s_bs[t] = bs;
-        s_a[t] = a;
+        if constexpr (SR::kValues) s_a[t] = a;
         if (t == T - 1) s_off[T] = total;
         if constexpr (T == WG) __syncthreads(); else wave_lds_sync();
         if (stride) {
             const int g = t / NUM_G, l = t % NUM_G;
             for (int x = g; x < nv; x += T / NUM_G) {
                 const int b0 = s_bs[x], n = s_off[x + 1] - s_off[x];
-                const double ax = s_a[x];
+                const double ax = sr_load<SR>(s_a, x);
                 for (int q = l; q < n; q += NUM_G) add(b0 + q, ax, true);
             }
         } else {
@@ -175,7 +182,7 @@ __device__ __forceinline__ void for_products(const NumOps &o, int e0, int e1, in
                 }
 #pragma unroll
                 for (int u = 0; u < NUM_ILP; ++u)
-                    add(s_bs[x[u]] + (it[u] - s_off[x[u]]), s_a[x[u]], it0 + u * T < total);
+                    add(s_bs[x[u]] + (it[u] - s_off[x[u]]), sr_load<SR>(s_a, x[u]), it0 + u * T < total);
             }
         }
         if constexpr (T == WG) __syncthreads(); else wave_lds_sync();
@@ -184,9 +191,10 @@ __device__ __forceinline__ void for_products(const NumOps &o, int e0, int e1, in
 
 // T threads per row (16: packed, 64: wave, 256: workgroup), CAP pattern entries
 // at most (the class's len_C cap; the length is clamped to it, so LDS indices
-// stay in range whatever the list holds).  The row's columns and zeroed sums sit
-// in LDS; a product's column is found by a binary search there.
-template <int T, int CAP>
+// stay in range whatever the list holds).  The row's columns and its sums,
+// started at the semiring's identity, sit in LDS; a product's column is found by
+// a binary search there.
+template <class SR, int T, int CAP>
 __global__ __launch_bounds__(WG) void k_num_rows(const int *list, int nrows, NumOps o) {
     constexpr int SLOTS = WG / T, WALK = T;
     __shared__ int s_col[SLOTS][CAP];
@@ -208,21 +216,21 @@ __global__ __launch_bounds__(WG) void k_num_rows(const int *list, int nrows, Num
     double *acc = s_acc[slot];
     for (int q = t; q < len; q += T) {
         col[q] = o.ciC[c0 + q];
-        acc[q] = 0.0;
+        acc[q] = SR::identity();
     }
     if constexpr (T == WG) __syncthreads(); else wave_lds_sync();
     int bad = 0;
     auto add = [&](int q, double a, bool commit) {
         const int j = o.ciB[q];
-        const double x = a * o.b_val[q];
+        const double x = SR::mul(a, sr_load<SR>(o.b_val, q));
         const int pos = lower_bound_u(col, 0, len, j);
         const bool hit = pos < len && col[pos] == j;
         if (commit) {
-            if (hit) atomicAdd(&acc[pos], x);
+            if (hit) SR::atomic(&acc[pos], x);
             else bad = 1;
         }
     };
-    for_products<T>(o, e0, e1, t, s_off[slot], s_bs[slot], s_a[slot], s_red, add);
+    for_products<T, SR>(o, e0, e1, t, s_off[slot], s_bs[slot], s_a[slot], s_red, add);
     if constexpr (T == WG) __syncthreads(); else wave_lds_sync();
     for (int q = t; q < len; q += T) o.c_val[c0 + q] = acc[q];
     if (bad) atomicAdd(o.miss, 1);
@@ -238,6 +246,7 @@ __global__ __launch_bounds__(WG) void k_num_rows(const int *list, int nrows, Num
 // of the row's A entries -- loaded one per lane, then broadcast entry by entry
 // -- and its 64 lanes take the entry's B row.
 constexpr int NUM_WIN = kNumWindow;
+template <class SR>
 __global__ __launch_bounds__(WG) void k_num_row_win(const int *list, int nrows, NumOps o) {
     __shared__ double acc[NUM_WIN];
     __shared__ u32 bits[NUM_WIN / 32];
@@ -249,7 +258,7 @@ __global__ __launch_bounds__(WG) void k_num_row_win(const int *list, int nrows, 
         cmin = o.ciC[c0];
         span = max(min(o.ciC[c0 + len - 1] - cmin + 1, NUM_WIN), 0);  // (clamped: LDS indices stay in range)
     }
-    for (int q = tid; q < span; q += WG) acc[q] = 0.0;
+    for (int q = tid; q < span; q += WG) acc[q] = SR::identity();
     for (int q = tid; q < (span + 31) / 32; q += WG) bits[q] = 0u;
     __syncthreads();
     for (int q = tid; q < len; q += WG) {
@@ -263,14 +272,15 @@ __global__ __launch_bounds__(WG) void k_num_row_win(const int *list, int nrows, 
     // Lane l holds entries l and l + 64 of the current B row (rows of at most 128
     // entries).  While the next B row has the same length and, on every lane, the
     // same columns (one ballot) -- in FEM operands the dof rows of one node:
-    // cant's rows 3u, 3u+1, 3u+2 -- its a*b is added in registers; only a change
+    // cant's rows 3u, 3u+1, 3u+2 -- its a*b is added in registers (a (x) b and (+)
+    // of the semiring); only a change
     // of pattern sends the sums to the window: one ds_add_f64 per column per run
     // of equal B rows instead of one per product (the banded path's walk).
     constexpr int NONE = INT_MIN;  // (no column: col - cmin of valid columns is never this)
     int bad = 0, pc0 = NONE, pc1 = NONE, plen = -1;
     double px0 = 0.0, px1 = 0.0;
     auto put = [&](int d, double x) {
-        if ((unsigned)d < (unsigned)span && (bits[d >> 5] >> (d & 31) & 1u)) atomicAdd(&acc[d], x);
+        if ((unsigned)d < (unsigned)span && (bits[d >> 5] >> (d & 31) & 1u)) SR::atomic(&acc[d], x);
         else bad = 1;
     };
     auto flush = [&]() {
@@ -285,7 +295,7 @@ __global__ __launch_bounds__(WG) void k_num_row_win(const int *list, int nrows, 
             const int k = o.ciA[my];
             bs = o.rpB[k];
             be = o.rpB[k + 1];
-            av = o.a_val[my];
+            av = sr_load<SR>(o.a_val, my);
         }
         const int nj = min(64, e1 - base);
         for (int j = 0; j < nj; ++j) {
@@ -296,22 +306,22 @@ __global__ __launch_bounds__(WG) void k_num_row_win(const int *list, int nrows, 
                 flush();
                 pc0 = pc1 = NONE;
                 plen = -1;
-                for (int q = s + lane; q < e; q += 64) put(o.ciB[q] - cmin, a * o.b_val[q]);
+                for (int q = s + lane; q < e; q += 64) put(o.ciB[q] - cmin, SR::mul(a, sr_load<SR>(o.b_val, q)));
                 continue;
             }
             int d0 = NONE, d1 = NONE;
             double x0 = 0.0, x1 = 0.0;
             if (s + lane < e) {
                 d0 = o.ciB[s + lane] - cmin;
-                x0 = a * o.b_val[s + lane];
+                x0 = SR::mul(a, sr_load<SR>(o.b_val, s + lane));
             }
             if (s + 64 + lane < e) {
                 d1 = o.ciB[s + 64 + lane] - cmin;
-                x1 = a * o.b_val[s + 64 + lane];
+                x1 = SR::mul(a, sr_load<SR>(o.b_val, s + 64 + lane));
             }
             if (n == plen && __ballot(d0 != pc0 || d1 != pc1) == 0ull) {
-                px0 += x0;
-                px1 += x1;
+                px0 = SR::add(px0, x0);
+                px1 = SR::add(px1, x1);
             } else {
                 flush();
                 pc0 = d0;
@@ -326,21 +336,23 @@ __global__ __launch_bounds__(WG) void k_num_row_win(const int *list, int nrows, 
     __syncthreads();
     for (int q = tid; q < len; q += WG) {
         const int d = o.ciC[c0 + q] - cmin;
-        o.c_val[c0 + q] = (unsigned)d < (unsigned)span ? acc[d] : 0.0;
+        o.c_val[c0 + q] = (unsigned)d < (unsigned)span ? acc[d] : SR::identity();
     }
     if (bad) atomicAdd(o.miss, 1);
 }
 
-// the split rows' c_val segments := 0 (a workgroup per row)
-__global__ __launch_bounds__(WG) void k_num_zero(const int *list, int nrows, const int *rpC, double *c_val) {
+// the split rows' c_val segments := the run's semiring's identity (a workgroup per row)
+__global__ __launch_bounds__(WG) void k_num_fill(const int *list, int nrows, const int *rpC, double *c_val,
+                                                 double identity) {
     const int row = list[blockIdx.x];
     const int c1 = rpC[row + 1];
-    for (int q = rpC[row] + threadIdx.x; q < c1; q += WG) c_val[q] = 0.0;
+    for (int q = rpC[row] + threadIdx.x; q < c1; q += WG) c_val[q] = identity;
 }
 
 // one split unit per workgroup: (row, first A entry, A entries, w); w >= 0: the
 // one entry's B row from its w-th entry on, kNumUnitProducts entries at most;
 // w < 0: the entries' whole B rows
+template <class SR>
 __global__ __launch_bounds__(WG) void k_num_split(const int4 *units, NumOps o) {
     __shared__ int s_off[WG + 1], s_bs[WG], s_red[WAVES];
     __shared__ double s_a[WG];
@@ -349,22 +361,22 @@ __global__ __launch_bounds__(WG) void k_num_split(const int4 *units, NumOps o) {
     int bad = 0;
     auto add = [&](int q, double a, bool commit) {
         const int j = o.ciB[q];
-        const double x = a * o.b_val[q];
+        const double x = SR::mul(a, sr_load<SR>(o.b_val, q));
         const int pos = lower_bound_u(o.ciC, c0, c1, j);  // (c0, c1: the workgroup's own)
         const bool hit = pos < c1 && o.ciC[pos] == j;
         if (commit) {
-            if (hit) atomicAdd(&o.c_val[pos], x);
+            if (hit) SR::atomic(&o.c_val[pos], x);
             else bad = 1;
         }
     };
     if (u.w >= 0) {
         const int k = o.ciA[u.y];
-        const double a = o.a_val[u.y];
+        const double a = sr_load<SR>(o.a_val, u.y);
         const int b1 = o.rpB[k + 1], q0 = o.rpB[k] + u.w;
         const int q1 = b1 - q0 > kNumUnitProducts ? q0 + kNumUnitProducts : b1;
         for (int q = q0 + (int)threadIdx.x; q < q1; q += WG) add(q, a, true);
     } else {
-        for_products<WG>(o, u.y, u.y + u.z, (int)threadIdx.x, s_off, s_bs, s_a, s_red, add);
+        for_products<WG, SR>(o, u.y, u.y + u.z, (int)threadIdx.x, s_off, s_bs, s_a, s_red, add);
     }
     if (bad) atomicAdd(o.miss, 1);
 }
@@ -561,35 +573,59 @@ int dev_numeric_plan_create(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr
     return TSG_OK;
 }
 
+// the run's launches for one semiring (dev_numeric_run's order)
+template <class SR> static void numeric_launch(const NumericPlan &p, const NumOps &o, hipStream_t s) {
+    const auto list = [&](int l) { return p.rows + p.loff[l]; };
+    const auto n = [&](int l) { return p.lcnt[l]; };
+    // (the long rows first: their tails overlap the short rows' kernels)
+    if (n(kNumListSplit))
+        k_num_fill<<<n(kNumListSplit), WG, 0, s>>>(list(kNumListSplit), n(kNumListSplit), p.C.rowpointer, o.c_val,
+                                                   SR::identity());
+    // (a grid holds fewer than 2^32 threads: past kMaxGridBlocks units -- a LiveJournal-sized pattern's
+    // 3 * 10^7 -- the units go in several launches)
+    for (int u0 = 0; u0 < p.nunits; u0 += kMaxGridBlocks)
+        k_num_split<SR><<<std::min(p.nunits - u0, kMaxGridBlocks), WG, 0, s>>>(p.units + u0, o);
+    if (n(kNumListWg)) k_num_rows<SR, WG, kNumWgLen><<<n(kNumListWg), WG, 0, s>>>(list(kNumListWg), n(kNumListWg), o);
+    if (n(kNumListWgSmall))
+        k_num_rows<SR, WG, kNumWgSmallLen><<<n(kNumListWgSmall), WG, 0, s>>>(list(kNumListWgSmall), n(kNumListWgSmall), o);
+    if (n(kNumListWaveSmall))
+        k_num_rows<SR, 64, kNumWaveSmallLen><<<(n(kNumListWaveSmall) + 3) / 4, WG, 0, s>>>(list(kNumListWaveSmall), n(kNumListWaveSmall), o);
+    if (n(kNumListWave))
+        k_num_rows<SR, 64, kNumWaveLen><<<(n(kNumListWave) + 3) / 4, WG, 0, s>>>(list(kNumListWave), n(kNumListWave), o);
+    if (n(kNumListWaveWin))
+        k_num_row_win<SR><<<n(kNumListWaveWin), WG, 0, s>>>(list(kNumListWaveWin), n(kNumListWaveWin), o);
+    if (n(kNumListPacked))
+        k_num_rows<SR, 16, kNumPackedLen><<<(n(kNumListPacked) + 15) / 16, WG, 0, s>>>(list(kNumListPacked), n(kNumListPacked), o);
+}
+
+int semiring_identity(int semiring, double *identity) {
+    return semiring_dispatch(semiring, [&](auto sr) {
+        *identity = decltype(sr)::identity();
+        return TSG_OK;
+    });
+}
+
+bool semiring_known(int semiring) {
+    double id;
+    return semiring_identity(semiring, &id) == TSG_OK;
+}
+
 // Queued on s and waited for: no allocation, no read-back before the final
 // wait, every geometry from the plan.  ev (optional): ev[4]..ev[5] bracket the
-// numeric kernels.  *missed: products whose column the pattern lacks.
-int dev_numeric_run(Context &cx, NumericPlan &p, const double *a_val, const double *b_val, double *c_val,
-                    hipStream_t s, hipEvent_t *ev, int *missed) {
+// numeric kernels.  *missed: products whose column the pattern lacks.  An
+// unknown semiring: TSG_ERR_INVALID, nothing queued.
+int dev_numeric_run(Context &cx, NumericPlan &p, int semiring, const double *a_val, const double *b_val,
+                    double *c_val, hipStream_t s, hipEvent_t *ev, int *missed) {
     (void)cx;
+    if (!semiring_known(semiring)) return TSG_ERR_INVALID;
     const NumOps o{p.A.rowpointer, p.A.columnindex, p.B.rowpointer, p.B.columnindex, p.C.rowpointer,
                    p.C.columnindex, a_val, b_val, c_val, p.miss};
     TSG_HIP(hipMemsetAsync(p.miss, 0, sizeof(int), s));
     if (ev) TSG_HIP(hipEventRecord(ev[4], s));
-    const auto list = [&](int l) { return p.rows + p.loff[l]; };
-    const auto n = [&](int l) { return p.lcnt[l]; };
-    // (the long rows first: their tails overlap the short rows' kernels)
-    if (n(kNumListSplit)) k_num_zero<<<n(kNumListSplit), WG, 0, s>>>(list(kNumListSplit), n(kNumListSplit), p.C.rowpointer, c_val);
-    // (a grid holds fewer than 2^32 threads: past kMaxGridBlocks units -- a LiveJournal-sized pattern's
-    // 3 * 10^7 -- the units go in several launches)
-    for (int u0 = 0; u0 < p.nunits; u0 += kMaxGridBlocks)
-        k_num_split<<<std::min(p.nunits - u0, kMaxGridBlocks), WG, 0, s>>>(p.units + u0, o);
-    if (n(kNumListWg)) k_num_rows<WG, kNumWgLen><<<n(kNumListWg), WG, 0, s>>>(list(kNumListWg), n(kNumListWg), o);
-    if (n(kNumListWgSmall))
-        k_num_rows<WG, kNumWgSmallLen><<<n(kNumListWgSmall), WG, 0, s>>>(list(kNumListWgSmall), n(kNumListWgSmall), o);
-    if (n(kNumListWaveSmall))
-        k_num_rows<64, kNumWaveSmallLen><<<(n(kNumListWaveSmall) + 3) / 4, WG, 0, s>>>(list(kNumListWaveSmall), n(kNumListWaveSmall), o);
-    if (n(kNumListWave))
-        k_num_rows<64, kNumWaveLen><<<(n(kNumListWave) + 3) / 4, WG, 0, s>>>(list(kNumListWave), n(kNumListWave), o);
-    if (n(kNumListWaveWin))
-        k_num_row_win<<<n(kNumListWaveWin), WG, 0, s>>>(list(kNumListWaveWin), n(kNumListWaveWin), o);
-    if (n(kNumListPacked))
-        k_num_rows<16, kNumPackedLen><<<(n(kNumListPacked) + 15) / 16, WG, 0, s>>>(list(kNumListPacked), n(kNumListPacked), o);
+    (void)semiring_dispatch(semiring, [&](auto sr) {
+        numeric_launch<decltype(sr)>(p, o, s);
+        return TSG_OK;
+    });
     TSG_HIP(hipGetLastError());
     if (ev) TSG_HIP(hipEventRecord(ev[5], s));
     TSG_HIP(hipMemcpyAsync(p.hmiss, p.miss, sizeof(int), hipMemcpyDeviceToHost, s));

@@ -10,6 +10,9 @@ import numpy as np
 import weakref
 
 from ._lib import DevCSR, MaskedInfo, NumericInfo, PoolStats, Stats, SymbolicInfo, TsgError, check, lib
+from .tilespgemm import SEMIRINGS
+
+_PLUS_PAIR = SEMIRINGS["plus_pair"]
 
 
 class DeviceCSR:
@@ -46,6 +49,36 @@ class DeviceCSR:
                 self.val.cpu().numpy() if self.val is not None else None)
 
 
+def _semiring(semiring):
+    """the TSG_SEMIRING_* value of a name or a value (an unknown value is passed
+    on: the library answers TSG_ERR_INVALID)"""
+    if isinstance(semiring, str):
+        try:
+            return SEMIRINGS[semiring]
+        except KeyError:
+            raise ValueError(f"unknown semiring {semiring!r}: one of {sorted(SEMIRINGS)}") from None
+    return int(semiring)
+
+
+def _run_values(plan, a_val, b_val, out, nout, sr):
+    """checks a run's value tensors; returns (a pointer, b pointer, out).  The
+    values may be None for the semiring that reads none ("plus_pair")."""
+    import torch
+    f64 = torch.float64
+    ptrs = [None, None]
+    for i, (t, n) in enumerate(((a_val, plan.A.nnz), (b_val, plan.B.nnz))):
+        if t is None and sr == _PLUS_PAIR:
+            continue
+        if t is None or t.dtype != f64 or not t.is_contiguous() or t.numel() != n or not t.is_cuda:
+            raise ValueError("values: contiguous float64 device tensors of the patterns' nnz")
+        ptrs[i] = t.data_ptr()
+    if out is None:
+        out = torch.empty(nout, dtype=f64, device=plan.A.rowptr.device)
+    elif out.dtype != f64 or not out.is_contiguous() or out.numel() != nout or not out.is_cuda:
+        raise ValueError(f"out: a contiguous float64 device tensor of {nout} entries")
+    return ptrs[0], ptrs[1], out
+
+
 class NumericPlan:
     """A tsg_numeric_plan: C = A*B's values on a known C pattern, for products
     repeated with fixed patterns and changing values.  Holds the three pattern
@@ -64,24 +97,22 @@ class NumericPlan:
         self.info = info.as_dict()
         self.nnzC = Cpattern.nnz
 
-    def run(self, a_val, b_val, out=None, stream=None, raw=False):
+    def run(self, a_val, b_val, out=None, stream=None, raw=False, semiring="plus_times"):
         """out[0:nnzC] := values of A*B for the f64 device tensors a_val / b_val
         laid on the plan's patterns.  Returns (out, stats).  Raises TsgError
-        (TSG_ERR_INVALID) when the pattern lacks a column of A*B."""
-        import torch
+        (TSG_ERR_INVALID) when the pattern lacks a column of A*B.  semiring: a
+        name of tilespgemm.SEMIRINGS or a TSG_SEMIRING_* value -- the sum and
+        the product of that semiring, its identity where no product reaches;
+        "plus_pair" reads no values (a_val / b_val may be None); an unknown
+        value raises TsgError (TSG_ERR_INVALID) with out untouched."""
         if not self.ptr:
             raise RuntimeError("numeric plan is closed")
-        for t, n in ((a_val, self.A.nnz), (b_val, self.B.nnz)):
-            if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != n or not t.is_cuda:
-                raise ValueError("values: contiguous float64 device tensors of the patterns' nnz")
-        if out is None:
-            out = torch.empty(self.nnzC, dtype=torch.float64, device=a_val.device)
-        elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != self.nnzC or not out.is_cuda:
-            raise ValueError("out: a contiguous float64 device tensor of nnzC entries")
+        sr = _semiring(semiring)
+        pa, pb, out = _run_values(self, a_val, b_val, out, self.nnzC, sr)
         st = Stats()
         s = C.c_void_p(stream) if stream else None
-        check("tsg_dev_numeric_run", lib().tsg_dev_numeric_run(
-            self.ctx.ptr, self.ptr, a_val.data_ptr(), b_val.data_ptr(), out.data_ptr(), s, C.byref(st)))
+        check("tsg_dev_numeric_run_semiring", lib().tsg_dev_numeric_run_semiring(
+            self.ctx.ptr, self.ptr, sr, pa, pb, out.data_ptr(), s, C.byref(st)))
         return out, (st if raw else st.as_dict())
 
     def close(self):
@@ -117,24 +148,20 @@ class MaskedPlan:
         self.info = info.as_dict()
         self.nnzM = Mask.nnz
 
-    def run(self, a_val, b_val, out=None, stream=None, raw=False):
+    def run(self, a_val, b_val, out=None, stream=None, raw=False, semiring="plus_times"):
         """out[0:nnzM] := the entries of A*B at the mask's positions for the f64
         device tensors a_val / b_val laid on the plan's patterns (0.0 where no
-        product reaches).  Returns (out, stats)."""
-        import torch
+        product reaches).  Returns (out, stats).  semiring: as in
+        NumericPlan.run (the semiring's identity where no product reaches;
+        "plus_pair" takes None for a_val / b_val)."""
         if not self.ptr:
             raise RuntimeError("masked plan is closed")
-        for t, n in ((a_val, self.A.nnz), (b_val, self.B.nnz)):
-            if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != n or not t.is_cuda:
-                raise ValueError("values: contiguous float64 device tensors of the patterns' nnz")
-        if out is None:
-            out = torch.empty(self.nnzM, dtype=torch.float64, device=a_val.device)
-        elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != self.nnzM or not out.is_cuda:
-            raise ValueError("out: a contiguous float64 device tensor of nnzM entries")
+        sr = _semiring(semiring)
+        pa, pb, out = _run_values(self, a_val, b_val, out, self.nnzM, sr)
         st = Stats()
         s = C.c_void_p(stream) if stream else None
-        check("tsg_dev_masked_run", lib().tsg_dev_masked_run(
-            self.ctx.ptr, self.ptr, a_val.data_ptr(), b_val.data_ptr(), out.data_ptr(), s, C.byref(st)))
+        check("tsg_dev_masked_run_semiring", lib().tsg_dev_masked_run_semiring(
+            self.ctx.ptr, self.ptr, sr, pa, pb, out.data_ptr(), s, C.byref(st)))
         return out, (st if raw else st.as_dict())
 
     def close(self):
@@ -254,6 +281,22 @@ class Context:
         DeviceCSR with val=None)."""
         c, _, _ = self.spgemm_symbolic(A, B, "pattern", stream)
         return self.numeric_plan(A, B, self.to_torch(c, device=A.rowptr.device, stream=stream), stream)
+
+    def spgemm_semiring(self, A, B, semiring, stream=None):
+        """The full product of the DeviceCSRs A and B over a semiring (a name of
+        tilespgemm.SEMIRINGS or a TSG_SEMIRING_* value), from the operands
+        alone: spgemm_plan (the symbolic pass gives C's pattern, the same for
+        every semiring) plus one run; the plan is closed before returning.
+        Returns (DeviceCSR in torch tensors, the plan's info dict, stats dict).
+        "plus_pair" reads no values (A.val / B.val may be None)."""
+        sr = _semiring(semiring)
+        plan = self.spgemm_plan(A, B, stream)
+        try:
+            out, st = plan.run(A.val, B.val, stream=stream, semiring=sr)
+            Cp, info = plan.Cpattern, plan.info
+        finally:
+            plan.close()
+        return DeviceCSR(Cp.m, Cp.n, Cp.rowptr, Cp.col, out), info, st
 
     def rows_sorted(self, M, stream=None):
         """whether every row of the device CSR M is strictly column-sorted"""

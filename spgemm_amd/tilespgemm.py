@@ -14,7 +14,8 @@ kernels of libtsg.so through the C ABI (include/tsg.h):
   tile2csr(C, tm, tn)                                  tile2csr.h:72-140
   spgemm(A, B, tm, tn)               -> (Matrix, stats)  one-shot CSR -> CSR
   spgemm_numeric(A, B, C)            -> stats         values only, on C's known pattern
-  spgemm_masked(A, B, C, mode)       -> stats         A*B at the entries of the mask C only
+  spgemm_masked(A, B, C, mode, semiring) -> stats     A*B at the entries of the mask C only
+  spgemm_semiring(A, B, semiring)    -> (Matrix, stats)  the full product over a semiring
 
 Errors raise TsgError (the reference exits or silently misbehaves instead).
 """
@@ -38,6 +39,19 @@ PATH_SYMBOLIC = 6  # spgemm_symbolic / Context.spgemm_symbolic
 # symbolic modes (include/tsg.h TSG_SYMBOLIC_*): row pointers and columns | row pointers only
 SYMBOLIC_PATTERN, SYMBOLIC_COUNT = 0, 1
 SYMBOLIC_MODES = {"pattern": SYMBOLIC_PATTERN, "count": SYMBOLIC_COUNT}
+
+
+# semirings of the numeric and masked plans (include/tsg.h TSG_SEMIRING_*)
+SEMIRINGS = {"plus_times": 0, "min_plus": 1, "max_plus": 2, "max_times": 3, "max_min": 4, "min_max": 5,
+             "plus_pair": 6}
+
+
+def semiring_identity(name):
+    """the semiring's additive identity -- what an entry no product reaches gets:
+    0.0, +inf or -inf (name: a key of SEMIRINGS or a TSG_SEMIRING_* value)"""
+    out = C.c_double(0.0)
+    check("tsg_semiring_identity", lib().tsg_semiring_identity(SEMIRINGS.get(name, name), C.byref(out)))
+    return out.value
 
 
 def _view(ptr, n, dt):
@@ -178,16 +192,30 @@ def spgemm_numeric(A, B, Cm):
     return st.as_dict()
 
 
-def spgemm_masked(A, B, Cm, mode="auto"):
+def spgemm_masked(A, B, Cm, mode="auto", semiring="plus_times"):
     """Masked product: Cm's rowpointer / columnindex are the mask (strictly
     ascending columns per row), Cm's values are overwritten with the entries of
     A*B at the mask's positions (0.0 where no product reaches); products
     elsewhere are dropped.  mode: "auto", "rows" or "dot" (or a TSG_MASKED_*
-    value).  Returns the stats dict."""
+    value).  semiring: a key of SEMIRINGS (or a TSG_SEMIRING_* value): its sum
+    and product, its identity where no product reaches.  Returns the stats
+    dict."""
     st = Stats()
-    check("tsg_spgemm_csr_masked", lib().tsg_spgemm_csr_masked(C.byref(A.s), C.byref(B.s), C.byref(Cm.s),
-                                                               MASKED_MODES.get(mode, mode), C.byref(st)))
+    check("tsg_spgemm_csr_masked_semiring", lib().tsg_spgemm_csr_masked_semiring(
+        C.byref(A.s), C.byref(B.s), C.byref(Cm.s), MASKED_MODES.get(mode, mode), SEMIRINGS.get(semiring, semiring),
+        C.byref(st)))
     return st.as_dict()
+
+
+def spgemm_semiring(A, B, semiring):
+    """One-shot CSR -> CSR over a semiring (a key of SEMIRINGS or a
+    TSG_SEMIRING_* value): C's pattern is A*B's structural one, its values the
+    semiring's sums.  Returns (C Matrix, stats dict of the numeric run)."""
+    Cm = Matrix()
+    st = Stats()
+    check("tsg_spgemm_csr_semiring", lib().tsg_spgemm_csr_semiring(C.byref(A.s), C.byref(B.s), C.byref(Cm.s),
+                                                                   SEMIRINGS.get(semiring, semiring), C.byref(st)))
+    return Cm, st.as_dict()
 
 
 def spgemm_symbolic(A, B, mode="pattern"):

@@ -14,6 +14,28 @@ def csr_of_rows(m, n, rows):
     return m, n, rp, ci, vv
 
 
+def tile_row_groups(rng, n, sums):
+    """per-row column arrays of a 16 * len(sums) x n operand whose groups of 16
+    rows hold sums[g] entries: rows 3 and 11 of a group empty, row 7 with half
+    of the entries (at most n: a full row), the rest spread unevenly; a row's
+    columns drawn without repeats and kept in drawn (unsorted) order.  The
+    operand of tests/test_gpu_sort_tiers.py's tile-row cases and of the fixture
+    x_rect_wide_64x4096 (tests/golden/gen_extra_mtx.py)."""
+    rows = []
+    for L in sums:
+        w = rng.random(16)
+        w[[3, 7, 11]] = 0
+        heavy = min(L // 2, n)
+        lens = np.floor(w / w.sum() * (L - heavy)).astype(int)
+        lens[7] = heavy
+        light = [r for r in range(16) if r not in (3, 7, 11)]
+        for r in light[:L - lens.sum()]:  # (what flooring left over: fewer than 13)
+            lens[r] += 1
+        assert lens.sum() == L and lens.max() <= n
+        rows += [rng.choice(n, size=int(l), replace=False) for l in lens]
+    return rows
+
+
 def hub_rows_case():
     """(A, B, arows) of test_rows_hub_rows_windowed_and_dominant_run: hub rows
     (past 65,536 products) without a dominant run -- many runs over 1,500,000

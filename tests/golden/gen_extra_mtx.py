@@ -2,16 +2,21 @@
 edge cases the reference's own UnitTest/CSR2TILE fixtures do not cover:
 symmetric mirroring, pattern / integer value types, unsorted file order with
 duplicate entries, rectangular shapes (A*A^T), empty rows and empty tile rows,
-fully dense tiles, and multi-tile-row banded / power-law structure.
+fully dense tiles, multi-tile-row banded / power-law structure, and tile rows
+long enough for every tier of the device's segmented sort.
 
 Run:  python tests/golden/gen_extra_mtx.py   (writes tests/golden/fixtures/x_*.mtx)
 """
 import os
+import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "fixtures")
+for _p in (os.path.dirname(HERE), os.path.dirname(os.path.dirname(HERE))):  # tests/ (for _cases) and the repository
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
 
 
 def write(name, m, n, entries, field="real", sym="general", rng=None):
@@ -91,6 +96,15 @@ def main():
         for j in rng.choice(m, size=int(deg[i]), replace=True, p=w):
             ent.add((i, int(perm[j])))
     write("x_powerlaw_400", m, m, sorted(ent), rng=rng)
+
+    # wide 64 x 4096 (A*A^T only): tile rows of 513, 4,096, 4,097 and 17 entries at
+    # 16-row tiles, 4,609 and 4,114 at 32, 8,723 at 64 -- the segmented sort's
+    # tiers 2 to 4 (tsg_device.hip), up to three 4,096-key chunks; empty rows, a
+    # half-full row, file order unsorted inside rows (its own generator: the
+    # fixtures above keep their draws)
+    from _cases import tile_row_groups
+    rows = tile_row_groups(np.random.default_rng(4096), 4096, (513, 4096, 4097, 17))
+    write("x_rect_wide_64x4096", 64, 4096, [(i, int(j)) for i, r in enumerate(rows) for j in r], rng=rng)
 
 
 if __name__ == "__main__":

@@ -29,7 +29,8 @@ DRIVER = os.path.join(REPO, "oracle", "_ref", "ref_driver")
 TILES = [(16, 16), (32, 16), (32, 32)]
 # the remaining reference tile sides (16 | t <= 64), on a subset of fixtures
 TILES_EXTRA = [(48, 16), (16, 48), (48, 48), (64, 64), (64, 16)]
-EXTRA_FIXTURES = ("x_powerlaw_400", "x_banded_500", "x_rect_50x130", "x_dense_48", "random_0.1_36x36")
+EXTRA_FIXTURES = ("x_powerlaw_400", "x_banded_500", "x_rect_50x130", "x_dense_48", "random_0.1_36x36",
+                  "x_rect_wide_64x4096")
 
 _DT = {"i": np.int32, "h": np.uint16, "d": np.float64, "q": np.int64}
 

@@ -186,6 +186,15 @@ int tsg_spgemm_csr_masked(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatri
  * C->columnindex too).  stats may be NULL. */
 int tsg_spgemm_csr_symbolic(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, int mode, tsg_stats *stats);
 
+/* Masked symbolic product: the pattern of A*B restricted to the structural mask
+ * (complement = 0) or to its complement (complement = 1).  Uploads the patterns
+ * of A, B and Mask (no value field is read; all may be NULL), runs
+ * tsg_dev_spgemm_symbolic_masked (below) and downloads the result as
+ * tsg_spgemm_csr_symbolic does.  Mask->m == A->m, Mask->n == B->n, its columns
+ * strictly ascending per row.  stats may be NULL. */
+int tsg_spgemm_csr_symbolic_masked(const tsg_smatrix *A, const tsg_smatrix *B, const tsg_smatrix *Mask,
+                                   int complement, int mode, tsg_smatrix *C, tsg_stats *stats);
+
 /* ---- semirings of the numeric and masked plans ----
  * c(i,j) = (+) over the k with A(i,k) and B(k,j) both stored of A(i,k) (x)
  * B(k,j), for a semiring ((+), (x)) chosen per run (a plan holds patterns only:
@@ -232,6 +241,19 @@ int tsg_spgemm_csr_semiring(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smat
  * TSG_SEMIRING_PLUS_TIMES is tsg_spgemm_csr_masked itself. */
 int tsg_spgemm_csr_masked_semiring(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, int mode, int semiring,
                                    tsg_stats *stats);
+/* One shot host CSR -> host CSR with GraphBLAS mask semantics: C<Mask> (complement
+ * = 0) or C<!Mask> (complement = 1) = A (+).(x) B, holding exactly the entries
+ * that a product reaches and the mask admits.  Uploads A, B and the mask's
+ * pattern (Mask->value is not read), runs the masked symbolic pass, creates a
+ * masked plan (TSG_MASKED_AUTO) on its pattern, runs it once with the semiring,
+ * destroys it and downloads C.  C->rowpointer / columnindex / value are malloc'd
+ * like tsg_spgemm_csr's.  Every returned entry is reached by a product: none
+ * holds a (+)-identity that was merely filled in.  PLUS_PAIR: A->value /
+ * B->value are not read and may be NULL.  TSG_ERR_INVALID for an unknown
+ * semiring or a complement outside {0, 1} (nothing is launched).  stats
+ * (nullable): the masked run's. */
+int tsg_spgemm_csr_masked_sparse(const tsg_smatrix *A, const tsg_smatrix *B, const tsg_smatrix *Mask, int complement,
+                                 int semiring, tsg_smatrix *C, tsg_stats *stats);
 
 /* Frees every non-NULL pointer field and zeroes the struct (covers the
  * reference's matrix_destroy, src/csr2tile.h:509-518, and the CSR arrays). */
@@ -387,8 +409,10 @@ int tsg_dev_numeric_plan_destroy(tsg_context *ctx, tsg_numeric_plan *plan);
  * For callers that want A*B at known positions (triangle counting L*L<L>,
  * k-truss, clustering coefficients): only the mask's nnz values are computed
  * and written; the full product is neither formed nor allocated.  The mask is
- * structural (a CSR pattern); complemented or valued masks and accumulation
- * into an existing C are not supported.  A plan has the numeric plan's life
+ * structural (a CSR pattern) and taken in the plain sense.  For a complemented
+ * mask, or for C<M> with only the entries a product reaches, take the pattern
+ * from tsg_dev_spgemm_symbolic_masked (below) and create the plan on it; valued
+ * masks and accumulation into an existing C are not supported.  A plan has the numeric plan's life
  * cycle: patterns fixed at creation, values per run, device memory of its own
  * (it survives tsg_context_reset; tsg_context_destroy frees the plans still
  * alive).
@@ -483,6 +507,32 @@ typedef struct tsg_symbolic_info {
 int tsg_dev_spgemm_symbolic(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B,
                             int mode, void *stream, tsg_dev_csr *Cpattern,
                             tsg_symbolic_info *info /*nullable*/, tsg_stats *stats /*nullable*/);
+
+/* ---- masked symbolic SpGEMM: the exact pattern of C<M> and C<!M> ----
+ * tsg_dev_spgemm_symbolic under a structural mask: entry (i, j) is in C iff some
+ * k has A(i,k) and B(k,j) stored AND ((i, j) is in Mask) != complement.
+ * complement = 1 is the frontier step of BFS and its kin, N = F*A<!Visited>,
+ * whose pattern is not known in advance; complement = 0 gives C<M> without the
+ * mask entries no product reaches.  A masked plan created on the result drops
+ * exactly the products the mask excludes, over any semiring.
+ * The output is tsg_dev_spgemm_symbolic's: rowpointer, columns strictly
+ * ascending per row, value == NULL, context-owned, count-first, nothing sized
+ * by the products; the unmasked pattern is never formed.
+ * Mask: values never read (value may be NULL); validated on the device with A
+ * and B before anything indexes with it, as tsg_dev_masked_plan_create
+ * validates its mask (row pointers, columns in [0, n) and strictly ascending
+ * per row, Mask->m == A->m, Mask->n == B->n); a mask with nnz 0 may have
+ * columnindex == NULL.  A violation, a complement outside {0, 1} or an unknown
+ * mode returns TSG_ERR_INVALID.  A and B may have unsorted rows and repeated
+ * columns.
+ * info: products, rows_class and units are those of the unmasked product (the
+ * rows are classed by their products, which still bound their lengths); nnzC
+ * is the masked count, exact also on TSG_ERR_OVERFLOW, which is decided on it.
+ * stats as for tsg_dev_spgemm_symbolic (path = TSG_PATH_SYMBOLIC). */
+int tsg_dev_spgemm_symbolic_masked(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B,
+                                   const tsg_dev_csr *Mask, int complement /*0|1*/, int mode /*TSG_SYMBOLIC_**/,
+                                   void *stream, tsg_dev_csr *Cpattern, tsg_symbolic_info *info /*nullable*/,
+                                   tsg_stats *stats /*nullable*/);
 
 /* Copies between host and device (stream-ordered, synchronous on return). */
 int tsg_memcpy_h2d(tsg_context *ctx, void *dst, const void *src, size_t bytes, void *stream);

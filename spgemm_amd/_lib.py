@@ -139,6 +139,10 @@ _SIGS = {
                                  C.POINTER(Stats)], C.c_int),
     "tsg_spgemm_csr_masked_semiring": ([C.POINTER(SMatrix), C.POINTER(SMatrix), C.POINTER(SMatrix), C.c_int, C.c_int,
                                         C.POINTER(Stats)], C.c_int),
+    "tsg_spgemm_csr_symbolic_masked": ([C.POINTER(SMatrix), C.POINTER(SMatrix), C.POINTER(SMatrix), C.c_int, C.c_int,
+                                        C.POINTER(SMatrix), C.POINTER(Stats)], C.c_int),
+    "tsg_spgemm_csr_masked_sparse": ([C.POINTER(SMatrix), C.POINTER(SMatrix), C.POINTER(SMatrix), C.c_int, C.c_int,
+                                      C.POINTER(SMatrix), C.POINTER(Stats)], C.c_int),
     "tsg_matrix_destroy": ([C.POINTER(SMatrix)], None),
     "tsg_context_create": ([C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "tsg_context_destroy": ([C.c_void_p], C.c_int),
@@ -174,6 +178,9 @@ _SIGS = {
     "tsg_dev_masked_plan_destroy": ([C.c_void_p, C.c_void_p], C.c_int),
     "tsg_dev_spgemm_symbolic": ([C.c_void_p, C.POINTER(DevCSR), C.POINTER(DevCSR), C.c_int, C.c_void_p,
                                  C.POINTER(DevCSR), C.POINTER(SymbolicInfo), C.POINTER(Stats)], C.c_int),
+    "tsg_dev_spgemm_symbolic_masked": ([C.c_void_p, C.POINTER(DevCSR), C.POINTER(DevCSR), C.POINTER(DevCSR), C.c_int,
+                                        C.c_int, C.c_void_p, C.POINTER(DevCSR), C.POINTER(SymbolicInfo),
+                                        C.POINTER(Stats)], C.c_int),
     "tsg_memcpy_h2d": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
     "tsg_memcpy_d2h": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
     "tsg_memcpy_d2d": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),

@@ -1416,8 +1416,10 @@ int tsg_spgemm_csr_numeric(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatr
 }
 
 // ---- symbolic product: C's pattern without values (tsg_symbolic.hip)
-int tsg_dev_spgemm_symbolic(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B, int mode, void *stream,
-                            tsg_dev_csr *Cpattern, tsg_symbolic_info *info, tsg_stats *stats) {
+// Mask null: the plain pass; else the masked one in the sense of complement
+static int symbolic_call(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B, const tsg_dev_csr *Mask,
+                         int complement, int mode, void *stream, tsg_dev_csr *Cpattern, tsg_symbolic_info *info,
+                         tsg_stats *stats) {
     if (Cpattern) *Cpattern = tsg_dev_csr{};
     if (info) *info = tsg_symbolic_info{};
     if (!ctx || !A || !B || !Cpattern) return TSG_ERR_INVALID;
@@ -1425,8 +1427,10 @@ int tsg_dev_spgemm_symbolic(tsg_context *ctx, const tsg_dev_csr *A, const tsg_de
     read_knobs(cx);
     auto h0 = std::chrono::steady_clock::now();
     tsg_symbolic_info inf{};
-    const int rc = dev_result(dev_symbolic(cx, *A, *B, mode, *Cpattern, inf, (hipStream_t)stream, cx.ev), stream,
-                              Cpattern);
+    const int rc = dev_result(
+        Mask ? dev_symbolic_masked(cx, *A, *B, *Mask, complement, mode, *Cpattern, inf, (hipStream_t)stream, cx.ev)
+             : dev_symbolic(cx, *A, *B, mode, *Cpattern, inf, (hipStream_t)stream, cx.ev),
+        stream, Cpattern);
     if (info) *info = inf;  // (on TSG_ERR_OVERFLOW too: the exact nnz(C))
     if (rc == TSG_OK && stats) {
         auto h1 = std::chrono::steady_clock::now();
@@ -1440,6 +1444,22 @@ int tsg_dev_spgemm_symbolic(tsg_context *ctx, const tsg_dev_csr *A, const tsg_de
         *stats = st;
     }
     return rc;
+}
+
+int tsg_dev_spgemm_symbolic(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B, int mode, void *stream,
+                            tsg_dev_csr *Cpattern, tsg_symbolic_info *info, tsg_stats *stats) {
+    return symbolic_call(ctx, A, B, nullptr, 0, mode, stream, Cpattern, info, stats);
+}
+
+int tsg_dev_spgemm_symbolic_masked(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B,
+                                   const tsg_dev_csr *Mask, int complement, int mode, void *stream,
+                                   tsg_dev_csr *Cpattern, tsg_symbolic_info *info, tsg_stats *stats) {
+    if (!Mask) {
+        if (Cpattern) *Cpattern = tsg_dev_csr{};
+        if (info) *info = tsg_symbolic_info{};
+        return TSG_ERR_INVALID;
+    }
+    return symbolic_call(ctx, A, B, Mask, complement, mode, stream, Cpattern, info, stats);
 }
 
 int tsg_spgemm_csr_symbolic(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smatrix *C, int mode, tsg_stats *stats) {
@@ -1459,6 +1479,42 @@ int tsg_spgemm_csr_symbolic(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smat
     TSG_TRY(upload(ws, &dB.columnindex, B->columnindex, (size_t)B->nnz, s));
     TSG_HIP(hipStreamSynchronize(s));
     int rc = tsg_dev_spgemm_symbolic(lease.ctx(), &dA, &dB, mode, s, &dC, nullptr, stats);
+    if (rc == TSG_OK) {
+        memset(C, 0, sizeof(*C));
+        C->m = dC.m; C->n = dC.n; C->nnz = dC.nnz;
+        rc = download(&C->rowpointer, dC.rowpointer, (size_t)dC.m + 1, s);
+        if (rc == TSG_OK && dC.columnindex) rc = download(&C->columnindex, dC.columnindex, (size_t)dC.nnz, s);
+        if (rc == TSG_OK && hipStreamSynchronize(s) != hipSuccess) rc = TSG_ERR_HIP;
+    }
+    return rc;
+}
+
+// a host mask: its pattern alone (values never read)
+static bool host_mask_ok(const tsg_smatrix *M, const tsg_smatrix *A, const tsg_smatrix *B) {
+    return M->m == A->m && M->n == B->n && M->nnz >= 0 && M->rowpointer && (!M->nnz || M->columnindex);
+}
+static int upload_pattern(PoolScope &ws, const tsg_smatrix *M, tsg_dev_csr &d, hipStream_t s) {
+    d = tsg_dev_csr{M->m, M->n, M->nnz, nullptr, nullptr, nullptr};
+    TSG_TRY(upload(ws, &d.rowpointer, M->rowpointer, (size_t)M->m + 1, s));
+    return upload(ws, &d.columnindex, M->columnindex, (size_t)M->nnz, s);
+}
+
+int tsg_spgemm_csr_symbolic_masked(const tsg_smatrix *A, const tsg_smatrix *B, const tsg_smatrix *Mask, int complement,
+                                   int mode, tsg_smatrix *C, tsg_stats *stats) {
+    if (!A || !B || !Mask || !C || A->n != B->m) return TSG_ERR_INVALID;
+    if (A->nnz < 0 || B->nnz < 0 || A->m < 0 || B->m < 0 || !A->rowpointer || !B->rowpointer) return TSG_ERR_INVALID;
+    if ((A->nnz && !A->columnindex) || (B->nnz && !B->columnindex) || !host_mask_ok(Mask, A, B)) return TSG_ERR_INVALID;
+    HostLease lease;
+    TSG_TRY(lease.acquire());
+    Context &cx = lease.cx();
+    hipStream_t s = lease.stream();
+    PoolScope ws(cx);  // (the uploads; what the dev_* call keeps returns with the lease)
+    tsg_dev_csr dA, dB, dM, dC{};
+    TSG_TRY(upload_pattern(ws, A, dA, s));
+    TSG_TRY(upload_pattern(ws, B, dB, s));
+    TSG_TRY(upload_pattern(ws, Mask, dM, s));
+    TSG_HIP(hipStreamSynchronize(s));
+    int rc = tsg_dev_spgemm_symbolic_masked(lease.ctx(), &dA, &dB, &dM, complement, mode, s, &dC, nullptr, stats);
     if (rc == TSG_OK) {
         memset(C, 0, sizeof(*C));
         C->m = dC.m; C->n = dC.n; C->nnz = dC.nnz;
@@ -1602,6 +1658,41 @@ int tsg_spgemm_csr_semiring(const tsg_smatrix *A, const tsg_smatrix *B, tsg_smat
     TSG_TRY(tsg_dev_numeric_plan_create(lease.ctx(), &dA, &dB, &dC, s, &plan, nullptr));
     int rc = tsg_dev_numeric_run_semiring(lease.ctx(), plan, semiring, dA.value, dB.value, dC.value, s, stats);
     (void)tsg_dev_numeric_plan_destroy(lease.ctx(), plan);
+    if (rc == TSG_OK) {
+        memset(C, 0, sizeof(*C));
+        C->m = dC.m; C->n = dC.n; C->nnz = dC.nnz;
+        rc = download(&C->rowpointer, dC.rowpointer, (size_t)dC.m + 1, s);
+        if (rc == TSG_OK) rc = download(&C->columnindex, dC.columnindex, (size_t)dC.nnz, s);
+        if (rc == TSG_OK) rc = download(&C->value, dC.value, (size_t)dC.nnz, s);
+        if (rc == TSG_OK && hipStreamSynchronize(s) != hipSuccess) rc = TSG_ERR_HIP;
+    }
+    return rc;
+}
+
+// ---- C<M> / C<!M> with values on the exact masked pattern: masked symbolic pass, masked plan, one run
+int tsg_spgemm_csr_masked_sparse(const tsg_smatrix *A, const tsg_smatrix *B, const tsg_smatrix *Mask, int complement,
+                                 int semiring, tsg_smatrix *C, tsg_stats *stats) {
+    if (!A || !B || !Mask || !C || A->n != B->m) return TSG_ERR_INVALID;
+    if (!semiring_known(semiring) || (complement != 0 && complement != 1)) return TSG_ERR_INVALID;
+    const bool vals = semiring_reads_values(semiring);
+    if (!host_operand_ok(A, vals) || !host_operand_ok(B, vals) || !host_mask_ok(Mask, A, B)) return TSG_ERR_INVALID;
+    HostLease lease;
+    TSG_TRY(lease.acquire());
+    Context &cx = lease.cx();
+    hipStream_t s = lease.stream();
+    PoolScope ws(cx);  // (the uploads and C's values; what the dev_* calls keep returns with the lease)
+    tsg_dev_csr dA, dB, dM, dC{};
+    TSG_TRY(upload_operand(ws, A, vals, dA, s));
+    TSG_TRY(upload_operand(ws, B, vals, dB, s));
+    TSG_TRY(upload_pattern(ws, Mask, dM, s));
+    TSG_HIP(hipStreamSynchronize(s));
+    TSG_TRY(tsg_dev_spgemm_symbolic_masked(lease.ctx(), &dA, &dB, &dM, complement, TSG_SYMBOLIC_PATTERN, s, &dC,
+                                           nullptr, nullptr));
+    TSG_TRY(ws.get(&dC.value, (size_t)dC.nnz + 1));
+    tsg_masked_plan *plan = nullptr;
+    TSG_TRY(tsg_dev_masked_plan_create(lease.ctx(), &dA, &dB, &dC, TSG_MASKED_AUTO, s, &plan, nullptr));
+    int rc = tsg_dev_masked_run_semiring(lease.ctx(), plan, semiring, dA.value, dB.value, dC.value, s, stats);
+    (void)tsg_dev_masked_plan_destroy(lease.ctx(), plan);
     if (rc == TSG_OK) {
         memset(C, 0, sizeof(*C));
         C->m = dC.m; C->n = dC.n; C->nnz = dC.nnz;

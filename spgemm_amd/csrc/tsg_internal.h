@@ -525,6 +525,14 @@ __host__ __device__ inline int symbolic_row_list(long long products) {  // -1: n
 // (recorded in both modes).
 int dev_symbolic(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, int mode, tsg_dev_csr &C,
                  tsg_symbolic_info &info, hipStream_t s, hipEvent_t *ev);
+// The masked pass: the pattern of A*B restricted to the
+// structural mask M (comp = 0) or to its complement (comp = 1).  M is validated
+// with A and B as the masked plan validates its mask; its values are not read.
+// Classes, units and batches are dev_symbolic's (P still bounds a row's length);
+// info: products, rows_class and units of the unmasked product, nnzC the masked
+// count, on which TSG_ERR_OVERFLOW is decided.
+int dev_symbolic_masked(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &M, int comp,
+                        int mode, tsg_dev_csr &C, tsg_symbolic_info &info, hipStream_t s, hipEvent_t *ev);
 
 // read a device int / long long synchronously through pinned memory
 int read_i32(Context &cx, const int *d, int *h, hipStream_t s);

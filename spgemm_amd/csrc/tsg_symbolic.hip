@@ -37,7 +37,17 @@
 // bitmap and a set are unions.  All indices come from validated operands (dev_operands_validate
 // runs first), LDS indices are bounded by the classes' caps, which the classify
 // kernel applies to the device's own product counts.
+//
+// The masked pass (dev_symbolic_masked) keeps of every
+// row the columns in a structural mask's row, or those outside it.  It is the
+// MASKED instantiation of the count and fill kernels; classes, units and
+// batches are the same, since P still bounds a row's length.  packed and set
+// test a column against the mask row by a bounded search, once per distinct
+// column; the bitmap classes build the mask row's bits for a thread's 512
+// columns in registers (sym_mask_words) and cut its words down before they are
+// popcounted or ranked.  The mask is validated with the operands.
 #include <algorithm>
+#include <type_traits>
 
 #include "tsg_dev_common.h"
 
@@ -57,6 +67,22 @@ struct SymOps {
     int *rp;           // C's row pointers: counts before the scan
     int *ci;           // C's columns (fill)
 };
+// the masked pass's (section 3.11): the structural mask and the sense beside them.  The
+// MASKED instantiations take this one; the others keep SymOps, so their argument
+// layout -- and with it their code -- is what it was before there was a mask
+struct SymOpsMasked : SymOps {
+    const int *rpM, *ciM;
+    int comp;          // 0: keep the columns in the mask's row, 1: those outside it
+};
+template <bool MASKED> using SymOpsFor = std::conditional_t<MASKED, SymOpsMasked, SymOps>;
+
+// whether the masked pass keeps column c of a row whose mask row is ciM[m0, m1) (strictly ascending)
+__device__ __forceinline__ bool sym_keep(const SymOpsMasked &o, int m0, int m1, int c) {
+    const int p = lower_bound_dev(o.ciM, m0, m1, c);
+    return (p < m1 && o.ciM[p] == c) != (o.comp != 0);
+}
+// a row no column of which can be kept: the plain sense on an empty mask row
+__device__ __forceinline__ bool sym_row_dead(const SymOpsMasked &o, int m0, int m1) { return !o.comp && m0 == m1; }
 
 // the lanes per A entry for ne entries among T threads: as few groups as entries
 __device__ __forceinline__ int sym_group(int T, int ne) {
@@ -222,15 +248,21 @@ __global__ __launch_bounds__(WG) void k_sym_units(const int *list, int nrows, co
 // ---------------------------------------------------------------------------
 // packed class
 // ---------------------------------------------------------------------------
-template <bool FILL>
-__global__ __launch_bounds__(WG) void k_sym_packed(const int *list, int nrows, SymOps o) {
+template <bool FILL, bool MASKED>
+__global__ __launch_bounds__(WG) void k_sym_packed(const int *list, int nrows, SymOpsFor<MASKED> o) {
     constexpr int CAP = (int)kSymPackedProducts, L = 16;
     __shared__ int s_key[WG / L][CAP], s_uni[WG / L][CAP], s_n[WG / L];
     const int g = threadIdx.x / L, l = threadIdx.x % L;
     const long li = (long)blockIdx.x * (WG / L) + g;
     const bool have = li < nrows;
     const int row = have ? list[li] : 0;
-    const int a0 = have ? o.rpA[row] : 0, a1 = have ? o.rpA[row + 1] : 0;
+    const int a0 = have ? o.rpA[row] : 0;
+    int a1 = have ? o.rpA[row + 1] : 0;
+    int m0 = 0, m1 = 0;
+    if constexpr (MASKED) {
+        m0 = have ? o.rpM[row] : 0, m1 = have ? o.rpM[row + 1] : 0;
+        if (sym_row_dead(o, m0, m1)) a1 = a0;  // (no products gathered: the count is 0)
+    }
     int *key = s_key[g], *uni = s_uni[g];
     if (l == 0) s_n[g] = 0;
     wave_lds_sync();
@@ -253,6 +285,7 @@ __global__ __launch_bounds__(WG) void k_sym_packed(const int *list, int nrows, S
             const int x = key[p];
             bool first = true;
             for (int q = 0; q < p; ++q) first = first && key[q] != x;
+            if constexpr (MASKED) first = first && sym_keep(o, m0, m1, x);  // (dropped: as a repeat, ranked by no one)
             uni[p] = first ? x : INT_MAX;  // (no column is INT_MAX: columns lie below n)
             mine += first ? 1 : 0;
         }
@@ -284,8 +317,8 @@ __global__ __launch_bounds__(WG) void k_sym_packed(const int *list, int nrows, S
 // ---------------------------------------------------------------------------
 // set class: T threads per row (64: a wave, 256: the workgroup), CAP products at most
 // ---------------------------------------------------------------------------
-template <int T, int LOG_HS, bool FILL>
-__global__ __launch_bounds__(WG) void k_sym_set(const int *list, int nrows, SymOps o) {
+template <int T, int LOG_HS, bool FILL, bool MASKED>
+__global__ __launch_bounds__(WG) void k_sym_set(const int *list, int nrows, SymOpsFor<MASKED> o) {
     constexpr int SLOTS = WG / T, HS = 1 << LOG_HS, DN = FILL ? HS / 2 : 1;
     __shared__ int s_tab[SLOTS][HS];
     __shared__ int s_dense[SLOTS][DN];  // (fill) the set's columns, packed, then sorted
@@ -295,7 +328,13 @@ __global__ __launch_bounds__(WG) void k_sym_set(const int *list, int nrows, SymO
     const long li = (long)blockIdx.x * SLOTS + slot;
     const bool have = li < nrows;
     const int row = have ? list[li] : 0;
-    const int a0 = have ? o.rpA[row] : 0, a1 = have ? o.rpA[row + 1] : 0;
+    const int a0 = have ? o.rpA[row] : 0;
+    int a1 = have ? o.rpA[row + 1] : 0;
+    int m0 = 0, m1 = 0;
+    if constexpr (MASKED) {
+        m0 = have ? o.rpM[row] : 0, m1 = have ? o.rpM[row + 1] : 0;
+        if (sym_row_dead(o, m0, m1)) a1 = a0;  // (nothing walked: the count is 0; uniform over the row's threads)
+    }
     // the row's table: the power of two from 2 P slots up (64 at least, HS at most: P is within the class's cap)
     const long long P = have ? o.E[a1] - o.E[a0] : 0;
     int lg = 6;
@@ -312,8 +351,9 @@ __global__ __launch_bounds__(WG) void k_sym_set(const int *list, int nrows, SymO
         // bound only keeps a miscounted row from spinning)
         for (int probe = 0; probe < hs; ++probe) {
             const int old = atomicCAS(&tab[h], -1, c);
-            if (old == -1) {
-                ++added;
+            if (old == -1) {  // (once per distinct column: the mask is tested here)
+                if constexpr (MASKED) added += sym_keep(o, m0, m1, c) ? 1 : 0;
+                else ++added;
                 break;
             }
             if (old == c) break;
@@ -331,7 +371,9 @@ __global__ __launch_bounds__(WG) void k_sym_set(const int *list, int nrows, SymO
         // keys that sort last, sorted by a bitonic network as unsigned keys
         u32 *k = reinterpret_cast<u32 *>(s_dense[slot]);
         for (int q0 = 0; q0 < hs; q0 += T) {  // (hs is a multiple of 64: whole waves; one atomic per wave and step)
-            const int v = tab[q0 + t];
+            int v = tab[q0 + t];
+            if constexpr (MASKED)
+                if (v != -1 && !sym_keep(o, m0, m1, v)) v = -1;  // (the sort sees kept columns only)
             const u64 msk = __ballot(v != -1);
             if (msk) {
                 const int leader = __ffsll((long long)msk) - 1;
@@ -388,6 +430,30 @@ __device__ __forceinline__ int sym_load_words(const u32 *bm, u32 (&w)[SYM_WPT]) 
     return pop;
 }
 
+// masked pass: the thread's words, which stand for the columns [col0, col0 + 32 * SYM_WPT),
+// cut down to the columns the mask row ciM[m0, m1) keeps; the popcount of what is left.
+// One lower bound for col0, then the mask entries consumed while they fall in word k
+// (k static: the words stay in registers).  Count and fill, and a hub batch's re-mark,
+// apply it to the same words, so their ranks agree.
+__device__ __forceinline__ int sym_mask_words(const SymOpsMasked &o, int m0, int m1, int col0, u32 (&w)[SYM_WPT]) {
+    constexpr int NC = 32 * SYM_WPT;
+    int p = lower_bound_dev(o.ciM, m0, m1, col0);
+    int d = p < m1 ? o.ciM[p] - col0 : NC;  // the next mask entry's place among the thread's columns (>= 0)
+    int pop = 0;
+#pragma unroll
+    for (int k = 0; k < SYM_WPT; ++k) {
+        u32 mw = 0u;
+        while (d < (k + 1) * 32) {
+            mw |= 1u << (d - k * 32);
+            ++p;
+            d = p < m1 ? o.ciM[p] - col0 : NC;
+        }
+        w[k] &= o.comp ? ~mw : mw;
+        pop += __popc(w[k]);
+    }
+    return pop;
+}
+
 // the set bits of the thread's words as columns, ascending, from out on
 __device__ __forceinline__ void sym_emit(const u32 (&w)[SYM_WPT], int col0, int *out) {
 #pragma unroll
@@ -402,8 +468,8 @@ __device__ __forceinline__ void sym_emit(const u32 (&w)[SYM_WPT], int col0, int 
 
 // window class: a workgroup per (row, window) unit.  ucnt: the unit's columns;
 // uoff: its offset within its row (k_sym_unit_scan)
-template <bool FILL>
-__global__ __launch_bounds__(WG) void k_sym_window(const int4 *units, SymOps o, int bsorted, int *ucnt,
+template <bool FILL, bool MASKED>
+__global__ __launch_bounds__(WG) void k_sym_window(const int4 *units, SymOpsFor<MASKED> o, int bsorted, int *ucnt,
                                                    const int *uoff) {
     __shared__ __attribute__((aligned(16))) u32 bm[SYM_SEG];
     __shared__ int s_red[WAVES];
@@ -411,6 +477,14 @@ __global__ __launch_bounds__(WG) void k_sym_window(const int4 *units, SymOps o, 
     const int4 u = units[blockIdx.x];
     if (FILL && ucnt[blockIdx.x] == 0) return;  // (block-uniform)
     const int row = u.x, wlo = u.y;
+    int m0 = 0, m1 = 0;
+    if constexpr (MASKED) {
+        m0 = o.rpM[row], m1 = o.rpM[row + 1];
+        if (!FILL && sym_row_dead(o, m0, m1)) {  // (block-uniform; the fill has left through ucnt)
+            if (tid == 0) ucnt[blockIdx.x] = 0;
+            return;
+        }
+    }
     const int wn = min(u.z, kSymWindow);  // the window's columns: [wlo, wlo + wn), up to the row's last
     // (only the words the row's span reaches, rounded up to whole threads' shares, are zeroed and read)
     const int nwords = min(((wn + 31) / 32 + SYM_WPT - 1) / SYM_WPT * SYM_WPT, SYM_SEG);
@@ -436,7 +510,9 @@ __global__ __launch_bounds__(WG) void k_sym_window(const int4 *units, SymOps o, 
     __syncthreads();
     u32 w[SYM_WPT];
     const bool in = tid * SYM_WPT < nwords;
-    const int pop = in ? sym_load_words(bm, w) : 0;
+    int pop = in ? sym_load_words(bm, w) : 0;
+    if constexpr (MASKED)
+        if (pop) pop = sym_mask_words(o, m0, m1, wlo + tid * SYM_WPT * 32, w);
     if constexpr (!FILL) {
         const int tot = block_sum(pop, s_red);
         if (tid == 0) ucnt[blockIdx.x] = tot;
@@ -503,12 +579,21 @@ __global__ __launch_bounds__(WG) void k_sym_hub_set(const int *list, SymOps o, c
 }
 
 // grid: (segments, the batch's rows): the segment's set bits
-__global__ __launch_bounds__(WG) void k_sym_hub_seg(const u32 *bm, long wpr, int nseg, int *segcnt) {
+// (MASKED: of the columns the row's mask keeps; list, o: read by that instantiation alone)
+template <bool MASKED>
+__global__ __launch_bounds__(WG) void k_sym_hub_seg(const u32 *bm, long wpr, int nseg, int *segcnt, const int *list,
+                                                    SymOpsFor<MASKED> o) {
     __shared__ int s_red[WAVES];
     u32 w[SYM_WPT];
     const long w0 = (long)blockIdx.x * SYM_SEG;
     int pop = 0;
     if (w0 + (long)threadIdx.x * SYM_WPT < wpr) pop = sym_load_words(bm + (size_t)blockIdx.y * wpr + w0, w);
+    if constexpr (MASKED) {
+        if (pop) {
+            const int row = list[blockIdx.y];
+            pop = sym_mask_words(o, o.rpM[row], o.rpM[row + 1], (int)((w0 + (long)threadIdx.x * SYM_WPT) * 32), w);
+        }
+    }
     pop = block_sum(pop, s_red);
     if (threadIdx.x == 0) segcnt[(long)blockIdx.y * nseg + blockIdx.x] = pop;
 }
@@ -531,14 +616,21 @@ __global__ __launch_bounds__(WG) void k_sym_hub_rows(const int *list, int nrows,
 }
 
 // grid: (segments, the batch's rows): the segment's columns at their ranks
-__global__ __launch_bounds__(WG) void k_sym_hub_fill(const int *list, SymOps o, const u32 *bm, long wpr, int nseg,
-                                                     const int *segoff) {
+template <bool MASKED>
+__global__ __launch_bounds__(WG) void k_sym_hub_fill(const int *list, SymOpsFor<MASKED> o, const u32 *bm, long wpr,
+                                                     int nseg, const int *segoff) {
     __shared__ int s_red[WAVES];
     u32 w[SYM_WPT];
     const long w0 = (long)blockIdx.x * SYM_SEG;
     const bool in = w0 + (long)threadIdx.x * SYM_WPT < wpr;
     int pop = 0;
     if (in) pop = sym_load_words(bm + (size_t)blockIdx.y * wpr + w0, w);
+    if constexpr (MASKED) {
+        if (pop) {  // (the words the count ranked: the same mask again, on a batch's re-mark too)
+            const int row = list[blockIdx.y];
+            pop = sym_mask_words(o, o.rpM[row], o.rpM[row + 1], (int)((w0 + (long)threadIdx.x * SYM_WPT) * 32), w);
+        }
+    }
     int tot;
     const int off = block_excl_scan(pop, &tot, s_red);
     if (in && pop)
@@ -549,13 +641,21 @@ __global__ __launch_bounds__(WG) void k_sym_hub_fill(const int *list, SymOps o, 
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
-int dev_symbolic(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, int mode, tsg_dev_csr &C,
-                 tsg_symbolic_info &info, hipStream_t s, hipEvent_t *ev) {
+// MK: the masked pass (M, comp: its mask and sense; else M is null) -- the same host
+// steps over the kernels' MASKED instantiations
+template <bool MK>
+static int symbolic_run(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr *M, int comp,
+                        int mode, tsg_dev_csr &C, tsg_symbolic_info &info, hipStream_t s, hipEvent_t *ev) {
     C = tsg_dev_csr{};
     info = tsg_symbolic_info{};
     if (mode != TSG_SYMBOLIC_PATTERN && mode != TSG_SYMBOLIC_COUNT) return TSG_ERR_INVALID;
     bool bsorted = false;
-    TSG_TRY(dev_operands_validate(cx, A, B, &bsorted, s));
+    if constexpr (MK) {
+        if (comp != 0 && comp != 1) return TSG_ERR_INVALID;
+        TSG_TRY(dev_numeric_validate(cx, A, B, *M, &bsorted, s));  // (the mask as the masked plan validates its own)
+    } else {
+        TSG_TRY(dev_operands_validate(cx, A, B, &bsorted, s));
+    }
     info.b_rows_sorted = bsorted ? 1 : 0;
     const int m = A.m, n = B.n;
     PoolScope ws(cx);  // (temporaries and half-built outputs: back to the pool on every way out)
@@ -586,7 +686,9 @@ int dev_symbolic(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, int mo
     k_sym_entry_len<<<grid_for((long)A.nnz + 1, WG, 16384), WG, 0, s>>>(ebnd, A.nnz, E);
     TSG_HIP(hipGetLastError());
     TSG_TRY(dev_scan_i64(cx, E, (long)A.nnz + 1, s));
-    SymOps o{A.rowpointer, ebnd, E, B.columnindex, rp, nullptr};
+    SymOpsFor<MK> o{};
+    static_cast<SymOps &>(o) = SymOps{A.rowpointer, ebnd, E, B.columnindex, rp, nullptr};
+    if constexpr (MK) o.rpM = M->rowpointer, o.ciM = M->columnindex, o.comp = comp;
     TSG_HIP(hipMemsetAsync(nwin, 0, ((size_t)m + 1) * sizeof(long long), s));
     k_sym_classify<<<grid_for(m, WG * SYM_CPT, 16384), WG, 0, s>>>(A.rowpointer, E, m, rp, lists, cnt);
     k_sym_spans<<<grid_for(m, WAVES, 2048), WG, 0, s>>>(lists + (size_t)kSymListWindow * m, o, n, bsorted ? 1 : 0, win,
@@ -633,7 +735,7 @@ int dev_symbolic(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, int mo
         const int *hl = list_of(kSymListHub) + r0;
         TSG_HIP(hipMemsetAsync(bm, 0, (size_t)nr * wpr * sizeof(u32), s));
         k_sym_hub_set<<<dim3(std::max(1, std::min(256, 4096 / nr)), nr), WG, 0, s>>>(hl, o, E, bm, wpr);
-        k_sym_hub_seg<<<dim3(nseg, nr), WG, 0, s>>>(bm, wpr, nseg, segcnt);
+        k_sym_hub_seg<MK><<<dim3(nseg, nr), WG, 0, s>>>(bm, wpr, nseg, segcnt, hl, o);
         if (count) k_sym_hub_rows<true><<<(nr + WAVES - 1) / WAVES, WG, 0, s>>>(hl, nr, nseg, segcnt, rp);
         else k_sym_hub_rows<false><<<(nr + WAVES - 1) / WAVES, WG, 0, s>>>(hl, nr, nseg, segcnt, rp);
         TSG_HIP(hipGetLastError());
@@ -648,17 +750,19 @@ int dev_symbolic(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, int mo
     TSG_HIP(hipEventRecord(ev[4], s));
     for (int b = 0; b < nbatch; ++b) TSG_TRY(hub_marks(b * batch, std::min(batch, nhub - b * batch), true));
     for (int u0 = 0; u0 < nwu; u0 += kMaxGridBlocks)
-        k_sym_window<false><<<std::min(nwu - u0, kMaxGridBlocks), WG, 0, s>>>(units + u0, o, bsorted ? 1 : 0,
-                                                                             ucnt + u0, uoff + u0);
+        k_sym_window<false, MK><<<std::min(nwu - u0, kMaxGridBlocks), WG, 0, s>>>(units + u0, o, bsorted ? 1 : 0,
+                                                                                 ucnt + u0, uoff + u0);
     if (nwu)
         k_sym_unit_scan<<<grid_for(nwl, WAVES, 2048), WG, 0, s>>>(list_of(kSymListWindow), nwl, win, nwin, ucnt, uoff,
                                                                   rp);
-    rows_launch(kSymListSetWg, 1, [&](const int *l, int c) { k_sym_set<WG, 13, false><<<c, WG, 0, s>>>(l, c, o); });
+    rows_launch(kSymListSetWg, 1, [&](const int *l, int c) {
+        k_sym_set<WG, 13, false, MK><<<c, WG, 0, s>>>(l, c, o);
+    });
     rows_launch(kSymListSetWave, WAVES, [&](const int *l, int c) {
-        k_sym_set<64, 10, false><<<(c + WAVES - 1) / WAVES, WG, 0, s>>>(l, c, o);
+        k_sym_set<64, 10, false, MK><<<(c + WAVES - 1) / WAVES, WG, 0, s>>>(l, c, o);
     });
     rows_launch(kSymListPacked, 16, [&](const int *l, int c) {
-        k_sym_packed<false><<<(c + 15) / 16, WG, 0, s>>>(l, c, o);
+        k_sym_packed<false, MK><<<(c + 15) / 16, WG, 0, s>>>(l, c, o);
     });
     TSG_HIP(hipGetLastError());
     TSG_HIP(hipEventRecord(ev[5], s));
@@ -681,23 +785,35 @@ int dev_symbolic(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, int mo
     for (int b = 0; b < nbatch; ++b) {
         const int r0 = b * batch, nr = std::min(batch, nhub - r0);
         if (nbatch > 1) TSG_TRY(hub_marks(r0, nr, false));  // (one batch: the count's bitmaps and offsets still stand)
-        k_sym_hub_fill<<<dim3(nseg, nr), WG, 0, s>>>(list_of(kSymListHub) + r0, o, bm, wpr, nseg, segcnt);
+        k_sym_hub_fill<MK><<<dim3(nseg, nr), WG, 0, s>>>(list_of(kSymListHub) + r0, o, bm, wpr, nseg, segcnt);
     }
     for (int u0 = 0; u0 < nwu; u0 += kMaxGridBlocks)
-        k_sym_window<true><<<std::min(nwu - u0, kMaxGridBlocks), WG, 0, s>>>(units + u0, o, bsorted ? 1 : 0,
-                                                                            ucnt + u0, uoff + u0);
-    rows_launch(kSymListSetWg, 1, [&](const int *l, int c) { k_sym_set<WG, 13, true><<<c, WG, 0, s>>>(l, c, o); });
+        k_sym_window<true, MK><<<std::min(nwu - u0, kMaxGridBlocks), WG, 0, s>>>(units + u0, o, bsorted ? 1 : 0,
+                                                                                ucnt + u0, uoff + u0);
+    rows_launch(kSymListSetWg, 1, [&](const int *l, int c) {
+        k_sym_set<WG, 13, true, MK><<<c, WG, 0, s>>>(l, c, o);
+    });
     rows_launch(kSymListSetWave, WAVES, [&](const int *l, int c) {
-        k_sym_set<64, 10, true><<<(c + WAVES - 1) / WAVES, WG, 0, s>>>(l, c, o);
+        k_sym_set<64, 10, true, MK><<<(c + WAVES - 1) / WAVES, WG, 0, s>>>(l, c, o);
     });
     rows_launch(kSymListPacked, 16, [&](const int *l, int c) {
-        k_sym_packed<true><<<(c + 15) / 16, WG, 0, s>>>(l, c, o);
+        k_sym_packed<true, MK><<<(c + 15) / 16, WG, 0, s>>>(l, c, o);
     });
     TSG_HIP(hipGetLastError());
     TSG_HIP(hipEventRecord(ev[7], s));
     TSG_TRY(stream_wait(s));
     C = tsg_dev_csr{m, n, (int)total, ws.keep(rp), ws.keep(ci), nullptr};
     return TSG_OK;
+}
+
+int dev_symbolic(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, int mode, tsg_dev_csr &C,
+                 tsg_symbolic_info &info, hipStream_t s, hipEvent_t *ev) {
+    return symbolic_run<false>(cx, A, B, nullptr, 0, mode, C, info, s, ev);
+}
+
+int dev_symbolic_masked(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &M, int comp,
+                        int mode, tsg_dev_csr &C, tsg_symbolic_info &info, hipStream_t s, hipEvent_t *ev) {
+    return symbolic_run<true>(cx, A, B, &M, comp, mode, C, info, s, ev);
 }
 
 }  // namespace tsg

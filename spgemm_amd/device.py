@@ -253,7 +253,7 @@ class Context:
                                                          C.byref(c), C.byref(st)))
         return c, (st if raw else st.as_dict())
 
-    def spgemm_symbolic(self, A, B, mode="pattern", stream=None):
+    def spgemm_symbolic(self, A, B, mode="pattern", stream=None, mask=None, complement=False):
         """The structural pattern of A*B without values: (DevCSR struct with
         context-owned row pointers and -- mode "pattern" -- columns, value null;
         info dict; stats dict).  Valid until the next reset().  mode "count":
@@ -261,18 +261,53 @@ class Context:
         not read (DeviceCSRs with val=None are fine); their rows may be unsorted
         and repeat columns.  Raises TsgError: TSG_ERR_INVALID for malformed
         operands or an unknown mode; TSG_ERR_OVERFLOW when nnz(C) exceeds int32
-        -- the error's .info then still holds the exact nnzC."""
+        -- the error's .info then still holds the exact nnzC.
+        mask (a DeviceCSR; its values are not read, val=None is fine; columns
+        strictly ascending per row): the masked pass
+        (tsg_dev_spgemm_symbolic_masked) -- the pattern of A*B restricted to the
+        mask's entries, or with complement=True to the entries outside it (a
+        BFS step: spgemm_symbolic(F, A, mask=Visited, complement=True)).  info's
+        nnzC is then the masked count; products, rows_class and units stay the
+        unmasked product's.  complement: a bool, or an int passed through (the
+        library refuses values outside {0, 1})."""
         from .tilespgemm import SYMBOLIC_MODES
         a, b, c, info, st = A.struct(), B.struct(), DevCSR(), SymbolicInfo(), Stats()
         s = C.c_void_p(stream) if stream else None
         md = SYMBOLIC_MODES.get(mode, mode)
-        rc = lib().tsg_dev_spgemm_symbolic(self.ptr, C.byref(a), C.byref(b), md if isinstance(md, int) else -1, s,
-                                           C.byref(c), C.byref(info), C.byref(st))
+        md = md if isinstance(md, int) else -1
+        if mask is None:
+            name = "tsg_dev_spgemm_symbolic"
+            rc = lib().tsg_dev_spgemm_symbolic(self.ptr, C.byref(a), C.byref(b), md, s, C.byref(c), C.byref(info),
+                                               C.byref(st))
+        else:
+            name = "tsg_dev_spgemm_symbolic_masked"
+            mk = mask.struct()
+            rc = lib().tsg_dev_spgemm_symbolic_masked(self.ptr, C.byref(a), C.byref(b), C.byref(mk), int(complement),
+                                                      md, s, C.byref(c), C.byref(info), C.byref(st))
         if rc != 0:
-            err = TsgError("tsg_dev_spgemm_symbolic", rc)
+            err = TsgError(name, rc)
             err.info = info.as_dict()
             raise err
         return c, info.as_dict(), st.as_dict()
+
+    def spgemm_masked_sparse(self, A, B, Mask, complement=False, semiring="plus_times", mode="auto", stream=None):
+        """C<Mask> (or, complement=True, C<!Mask>) = A*B over a semiring with
+        GraphBLAS mask semantics: exactly the entries a product reaches and the
+        mask admits.  The masked symbolic pass gives the pattern, which is
+        copied into torch tensors; a masked plan on it (mode: the plan's,
+        "auto" by default) runs once and is closed before returning.  Returns
+        (DeviceCSR in torch tensors, the symbolic pass's info dict, the run's
+        stats dict).  "plus_pair" reads no values (A.val / B.val may be None);
+        Mask's values are never read."""
+        sr = _semiring(semiring)
+        c, info, _ = self.spgemm_symbolic(A, B, "pattern", stream, mask=Mask, complement=complement)
+        Cp = self.to_torch(c, device=A.rowptr.device, stream=stream)
+        plan = self.masked_plan(A, B, Cp, mode, stream)
+        try:
+            out, st = plan.run(A.val, B.val, stream=stream, semiring=sr)
+        finally:
+            plan.close()
+        return DeviceCSR(Cp.m, Cp.n, Cp.rowptr, Cp.col, out), info, st
 
     def spgemm_plan(self, A, B, stream=None):
         """A NumericPlan for C = A*B from the operands alone: the symbolic pass

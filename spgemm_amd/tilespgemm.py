@@ -16,6 +16,8 @@ kernels of libtsg.so through the C ABI (include/tsg.h):
   spgemm_numeric(A, B, C)            -> stats         values only, on C's known pattern
   spgemm_masked(A, B, C, mode, semiring) -> stats     A*B at the entries of the mask C only
   spgemm_semiring(A, B, semiring)    -> (Matrix, stats)  the full product over a semiring
+  spgemm_symbolic_masked(A, B, M, complement, mode) -> (Matrix, stats)  the pattern of A*B inside / outside M
+  spgemm_masked_sparse(A, B, M, complement, semiring) -> (Matrix, stats)  C<M> / C<!M>, reached entries only
 
 Errors raise TsgError (the reference exits or silently misbehaves instead).
 """
@@ -228,6 +230,34 @@ def spgemm_symbolic(A, B, mode="pattern"):
     st = Stats()
     check("tsg_spgemm_csr_symbolic", lib().tsg_spgemm_csr_symbolic(C.byref(A.s), C.byref(B.s), C.byref(Cm.s),
                                                                    SYMBOLIC_MODES.get(mode, mode), C.byref(st)))
+    return Cm, st.as_dict()
+
+
+def spgemm_symbolic_masked(A, B, Mask, complement=False, mode="pattern"):
+    """Masked symbolic product: the pattern of A*B restricted to the entries of
+    the structural mask (a Matrix with A's rows and B's columns, columns
+    strictly ascending per row; its values are not read), or with
+    complement=True to the entries outside it.  mode and the result as in
+    spgemm_symbolic."""
+    Cm = Matrix()
+    st = Stats()
+    check("tsg_spgemm_csr_symbolic_masked", lib().tsg_spgemm_csr_symbolic_masked(
+        C.byref(A.s), C.byref(B.s), C.byref(Mask.s), int(complement), SYMBOLIC_MODES.get(mode, mode), C.byref(Cm.s),
+        C.byref(st)))
+    return Cm, st.as_dict()
+
+
+def spgemm_masked_sparse(A, B, Mask, complement=False, semiring="plus_times"):
+    """One-shot C<Mask> (complement=True: C<!Mask>) = A*B over a semiring with
+    GraphBLAS mask semantics: C holds exactly the entries that a product
+    reaches and the mask admits -- none carries an identity that was merely
+    filled in (spgemm_masked writes one at every mask entry).  Returns (C
+    Matrix, stats dict of the masked run)."""
+    Cm = Matrix()
+    st = Stats()
+    check("tsg_spgemm_csr_masked_sparse", lib().tsg_spgemm_csr_masked_sparse(
+        C.byref(A.s), C.byref(B.s), C.byref(Mask.s), int(complement), SEMIRINGS.get(semiring, semiring),
+        C.byref(Cm.s), C.byref(st)))
     return Cm, st.as_dict()
 
 

@@ -88,6 +88,7 @@ typedef struct tsg_stats {
 #define TSG_PATH_NUMERIC 4 /* numeric-only run on a known C pattern (tsg_dev_numeric_run) */
 #define TSG_PATH_MASKED 5  /* masked run: A*B on a mask's pattern only (tsg_dev_masked_run) */
 #define TSG_PATH_SYMBOLIC 6 /* symbolic pass: C's pattern without values (tsg_dev_spgemm_symbolic) */
+#define TSG_PATH_EWISE 7    /* element-wise union / intersection / difference of two CSRs (tsg_dev_ewise) */
 
 /* ---------------- library / device ---------------- */
 const char *tsg_version(void);
@@ -255,6 +256,30 @@ int tsg_spgemm_csr_masked_semiring(const tsg_smatrix *A, const tsg_smatrix *B, t
 int tsg_spgemm_csr_masked_sparse(const tsg_smatrix *A, const tsg_smatrix *B, const tsg_smatrix *Mask, int complement,
                                  int semiring, tsg_smatrix *C, tsg_stats *stats);
 
+/* ---- element-wise combination of two CSRs (tsg_dev_ewise, below) ---- */
+#define TSG_EWISE_UNION      0  /* pattern A u B: op(alpha a, beta b) where both are stored, alpha a or beta b where one is */
+#define TSG_EWISE_INTERSECT  1  /* pattern A n B: op(alpha a, beta b) */
+#define TSG_EWISE_DIFFERENCE 2  /* pattern A \ B: alpha a; op, beta and B's values are not read */
+
+#define TSG_BINOP_PLUS 0
+#define TSG_BINOP_TIMES 1
+#define TSG_BINOP_MIN 2
+#define TSG_BINOP_MAX 3
+#define TSG_BINOP_FIRST 4   /* alpha a */
+#define TSG_BINOP_SECOND 5  /* beta b */
+
+/* "plus", "times", "min", "max", "first", "second"; NULL for an unknown op. */
+const char *tsg_binop_name(int op);
+
+/* One shot host CSR -> host CSR: uploads A and B, runs tsg_dev_ewise (below;
+ * its contract holds: A->m == B->m, A->n == B->n, strictly ascending columns
+ * per row, A->value == NULL for a structural call), downloads C.  C->rowpointer
+ * / columnindex / value are malloc'd like tsg_spgemm_csr's (columnindex and
+ * value NULL for an empty C, value NULL for a structural call).  stats may be
+ * NULL. */
+int tsg_ewise_csr(const tsg_smatrix *A, const tsg_smatrix *B, int mode, int op, double alpha, double beta,
+                  tsg_smatrix *C, tsg_stats *stats);
+
 /* Frees every non-NULL pointer field and zeroes the struct (covers the
  * reference's matrix_destroy, src/csr2tile.h:509-518, and the CSR arrays). */
 void tsg_matrix_destroy(tsg_smatrix *M);
@@ -411,8 +436,9 @@ int tsg_dev_numeric_plan_destroy(tsg_context *ctx, tsg_numeric_plan *plan);
  * and written; the full product is neither formed nor allocated.  The mask is
  * structural (a CSR pattern) and taken in the plain sense.  For a complemented
  * mask, or for C<M> with only the entries a product reaches, take the pattern
- * from tsg_dev_spgemm_symbolic_masked (below) and create the plan on it; valued
- * masks and accumulation into an existing C are not supported.  A plan has the numeric plan's life
+ * from tsg_dev_spgemm_symbolic_masked (below) and create the plan on it; to
+ * accumulate a product into an existing C, combine the two with tsg_dev_ewise
+ * (below).  Valued masks remain out of scope.  A plan has the numeric plan's life
  * cycle: patterns fixed at creation, values per run, device memory of its own
  * (it survives tsg_context_reset; tsg_context_destroy frees the plans still
  * alive).
@@ -533,6 +559,60 @@ int tsg_dev_spgemm_symbolic_masked(tsg_context *ctx, const tsg_dev_csr *A, const
                                    const tsg_dev_csr *Mask, int complement /*0|1*/, int mode /*TSG_SYMBOLIC_**/,
                                    void *stream, tsg_dev_csr *Cpattern, tsg_symbolic_info *info /*nullable*/,
                                    tsg_stats *stats /*nullable*/);
+
+/* ---- element-wise union, intersection and difference of two CSRs ----
+ * What sits between two products of a graph algorithm: Visited u= N of a BFS
+ * (structural union), D = min(D, D*A) of Bellman-Ford (union with MIN),
+ * alpha A + beta B (union with PLUS), and with them the accumulation of a
+ * product into an existing C.  C's pattern is A u B, A n B or A \ B (mode:
+ * TSG_EWISE_*, above); an entry stored in both operands holds op(alpha a, beta b)
+ * (op: TSG_BINOP_*), one stored in A alone alpha a, in B alone beta b.
+ * Count-first like the symbolic pass: the entries stored in both operands are
+ * counted per row (the columns alone are read), the counts scanned, then every
+ * column and value written once at its final place -- no staging sized by the
+ * operands, no compaction.
+ *  - Shapes and order: A->m == B->m and A->n == B->n; both operands have
+ *    strictly ascending columns per row (every output of this library has).
+ *    Both are validated on the device before anything indexes with them:
+ *    rowpointer[0] == 0, non-decreasing, rowpointer[m] == nnz, columns in
+ *    [0, n) and strictly ascending per row.  A violation, an unknown mode or an
+ *    unknown op returns TSG_ERR_INVALID with *C zeroed and nothing launched past
+ *    the validation.  An operand with nnz == 0 may have columnindex == NULL.
+ *  - Structural or valued: A->value == NULL makes the call structural:
+ *    C->value == NULL and no value, op or scalar is read.  Otherwise C has
+ *    values and B->value must be non-NULL -- except for TSG_EWISE_DIFFERENCE and
+ *    for TSG_BINOP_FIRST under TSG_EWISE_INTERSECT, which never read B's values
+ *    (B->value may be NULL).  Any other NULL value pointer (of an operand with
+ *    entries) is TSG_ERR_INVALID.
+ *  - Values: alpha a and beta b are each rounded once, then op is applied and
+ *    rounded once; nothing is contracted into a fused multiply-add.  MIN and
+ *    MAX are fmin / fmax; NaN inputs and the sign of a zero are unspecified, as
+ *    for the semirings.  No atomic takes part: every result is bit-reproducible.
+ *    Entries are structural: a stored 0.0 takes part and no result is dropped.
+ *  - Output: rowpointer, columnindex strictly ascending per row, and value;
+ *    context-owned, valid until tsg_context_reset, synchronous on return like
+ *    tsg_dev_spgemm's C.  An empty C has columnindex and value NULL.
+ *    nnz(C) > INT32_MAX returns TSG_ERR_OVERFLOW with C zeroed and info->nnzC
+ *    exact (the counts are summed in 64 bits).
+ * Rows are classed by L = len A_i + len B_i: packed (L <= 32, 16 lanes per
+ * row), wave (L <= 512, a wave per row) and tile (the rest: the row's merge
+ * cut into units of 2,048 merged entries, a workgroup each, so that one long
+ * row spreads over the whole device).
+ * The error contract of the tsg_dev_* calls holds.
+ * stats (nullable): path = TSG_PATH_EWISE, nnzCub = nnzA + nnzB (the entries
+ * merged), nnzC, t_e2e_ms, t_step3_kernel_ms (the count and fill kernels); the
+ * rest as in the numeric run. */
+typedef struct tsg_ewise_info {
+    long long nnzA, nnzB;
+    long long both;          /* entries stored in A and in B */
+    long long nnzC;          /* exact, also when it does not fit int32 */
+    long long rows_class[3]; /* rows per class: packed / wave / tile; rows with no entry in A or B are in none */
+    long long units;         /* work units of the class that cuts rows (tile) */
+} tsg_ewise_info;
+
+int tsg_dev_ewise(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B, int mode, int op,
+                  double alpha, double beta, void *stream, tsg_dev_csr *C,
+                  tsg_ewise_info *info /*nullable*/, tsg_stats *stats /*nullable*/);
 
 /* Copies between host and device (stream-ordered, synchronous on return). */
 int tsg_memcpy_h2d(tsg_context *ctx, void *dst, const void *src, size_t bytes, void *stream);

@@ -100,6 +100,16 @@ class SymbolicInfo(C.Structure):
                     units=self.units, b_rows_sorted=self.b_rows_sorted)
 
 
+class EwiseInfo(C.Structure):
+    """tsg_ewise_info, field for field."""
+    _fields_ = [("nnzA", C.c_longlong), ("nnzB", C.c_longlong), ("both", C.c_longlong), ("nnzC", C.c_longlong),
+                ("rows_class", C.c_longlong * 3), ("units", C.c_longlong)]
+
+    def as_dict(self):
+        return dict(nnzA=self.nnzA, nnzB=self.nnzB, both=self.both, nnzC=self.nnzC,
+                    rows_class=list(self.rows_class), units=self.units)
+
+
 class PoolStats(C.Structure):
     """tsg_pool_stats, field for field."""
     _fields_ = [(n, C.c_longlong) for n in ("live_blocks", "live_bytes", "reserved_bytes", "allocs")]
@@ -181,6 +191,11 @@ _SIGS = {
     "tsg_dev_spgemm_symbolic_masked": ([C.c_void_p, C.POINTER(DevCSR), C.POINTER(DevCSR), C.POINTER(DevCSR), C.c_int,
                                         C.c_int, C.c_void_p, C.POINTER(DevCSR), C.POINTER(SymbolicInfo),
                                         C.POINTER(Stats)], C.c_int),
+    "tsg_binop_name": ([C.c_int], C.c_char_p),
+    "tsg_ewise_csr": ([C.POINTER(SMatrix), C.POINTER(SMatrix), C.c_int, C.c_int, C.c_double, C.c_double,
+                       C.POINTER(SMatrix), C.POINTER(Stats)], C.c_int),
+    "tsg_dev_ewise": ([C.c_void_p, C.POINTER(DevCSR), C.POINTER(DevCSR), C.c_int, C.c_int, C.c_double, C.c_double,
+                       C.c_void_p, C.POINTER(DevCSR), C.POINTER(EwiseInfo), C.POINTER(Stats)], C.c_int),
     "tsg_memcpy_h2d": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
     "tsg_memcpy_d2h": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),
     "tsg_memcpy_d2d": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p], C.c_int),

@@ -1704,4 +1704,64 @@ int tsg_spgemm_csr_masked_sparse(const tsg_smatrix *A, const tsg_smatrix *B, con
     return rc;
 }
 
+// ---- element-wise union / intersection / difference of two CSRs (tsg_ewise.hip)
+const char *tsg_binop_name(int op) {
+    static const char *const names[] = {"plus", "times", "min", "max", "first", "second"};
+    return binop_known(op) ? names[op] : nullptr;
+}
+
+int tsg_dev_ewise(tsg_context *ctx, const tsg_dev_csr *A, const tsg_dev_csr *B, int mode, int op, double alpha,
+                  double beta, void *stream, tsg_dev_csr *C, tsg_ewise_info *info, tsg_stats *stats) {
+    if (C) *C = tsg_dev_csr{};
+    if (info) *info = tsg_ewise_info{};
+    if (!ctx || !A || !B || !C) return TSG_ERR_INVALID;
+    Context &cx = ctx->cx;
+    read_knobs(cx);
+    auto h0 = std::chrono::steady_clock::now();
+    tsg_ewise_info inf{};
+    const int rc = dev_result(dev_ewise(cx, *A, *B, mode, op, alpha, beta, *C, inf, (hipStream_t)stream, cx.ev),
+                              stream, C);
+    if (info) *info = inf;  // (on TSG_ERR_OVERFLOW too: the exact nnz(C))
+    if (rc == TSG_OK && stats) {
+        auto h1 = std::chrono::steady_clock::now();
+        tsg_stats st{};
+        st.numtileA = st.numtileB = st.numblkC = -1;
+        st.nnzCub = inf.nnzA + inf.nnzB;
+        st.nnzC = inf.nnzC;
+        st.path = TSG_PATH_EWISE;
+        st.t_step3_kernel_ms = ev_ms(cx.ev[4], cx.ev[5]) + ev_ms(cx.ev[6], cx.ev[7]);
+        st.t_e2e_ms = std::chrono::duration<double, std::milli>(h1 - h0).count();
+        *stats = st;
+    }
+    return rc;
+}
+
+int tsg_ewise_csr(const tsg_smatrix *A, const tsg_smatrix *B, int mode, int op, double alpha, double beta,
+                  tsg_smatrix *C, tsg_stats *stats) {
+    if (!A || !B || !C || A->m != B->m || A->n != B->n) return TSG_ERR_INVALID;
+    if (!ewise_mode_known(mode) || !binop_known(op)) return TSG_ERR_INVALID;
+    const bool valued = A->value != nullptr;  // (else structural: no value is uploaded)
+    const bool bvals = valued && ewise_reads_b_values(mode, op);
+    if (!host_operand_ok(A, false) || !host_operand_ok(B, bvals)) return TSG_ERR_INVALID;
+    HostLease lease;
+    TSG_TRY(lease.acquire());
+    Context &cx = lease.cx();
+    hipStream_t s = lease.stream();
+    PoolScope ws(cx);  // (the uploads; what the dev_* call keeps returns with the lease)
+    tsg_dev_csr dA, dB, dC{};
+    TSG_TRY(upload_operand(ws, A, valued, dA, s));
+    TSG_TRY(upload_operand(ws, B, bvals, dB, s));
+    TSG_HIP(hipStreamSynchronize(s));
+    int rc = tsg_dev_ewise(lease.ctx(), &dA, &dB, mode, op, alpha, beta, s, &dC, nullptr, stats);
+    if (rc == TSG_OK) {
+        memset(C, 0, sizeof(*C));
+        C->m = dC.m; C->n = dC.n; C->nnz = dC.nnz;
+        rc = download(&C->rowpointer, dC.rowpointer, (size_t)dC.m + 1, s);
+        if (rc == TSG_OK && dC.columnindex) rc = download(&C->columnindex, dC.columnindex, (size_t)dC.nnz, s);
+        if (rc == TSG_OK && dC.value) rc = download(&C->value, dC.value, (size_t)dC.nnz, s);
+        if (rc == TSG_OK && hipStreamSynchronize(s) != hipSuccess) rc = TSG_ERR_HIP;
+    }
+    return rc;
+}
+
 }  // extern "C"

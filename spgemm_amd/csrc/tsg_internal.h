@@ -154,6 +154,8 @@ struct HostSlots {
     long long hub_nmat;            //   the chunk x window offset matrix's
     unsigned long long fill_sizes; // the windowed fill lists' sizes (fill_sizes_pack)
     SymCounters sym;               // dev_symbolic: the class counts and unit totals
+    int ew_nlist[4];               // dev_ewise: the rows per launch list (kEwLists of them)
+    int unsorted[3];               // the patterns' validation: one sortedness flag per pattern (written by kernels)
 };
 
 struct Context {
@@ -229,7 +231,7 @@ class PoolScope {
 };
 
 // ---- launchers (all stream-ordered, no sync; in tsg_device.hip unless a
-// comment names tsg_band, tsg_rows, tsg_ctiles, tsg_tile_steps, tsg_numeric, tsg_masked or tsg_symbolic) ----
+// comment names tsg_band, tsg_rows, tsg_ctiles, tsg_tile_steps, tsg_numeric, tsg_masked, tsg_symbolic or tsg_ewise) ----
 // Exclusive scan in place over n elements (a[n-1] ends up = sum of a[0..n-2]
 // when the caller stored 0 there, i.e. the reference's "n+1 scan" idiom): the
 // generic three stages.
@@ -533,6 +535,36 @@ int dev_symbolic(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, int mo
 // count, on which TSG_ERR_OVERFLOW is decided.
 int dev_symbolic_masked(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &M, int comp,
                         int mode, tsg_dev_csr &C, tsg_symbolic_info &info, hipStream_t s, hipEvent_t *ev);
+
+// element-wise union / intersection / difference of two CSRs (tsg_ewise.hip,
+// DESIGN.md section 3.12), count-first: the entries stored in both operands
+// counted per row or unit, a scan, then every column and value written once at
+// its final place.  Rows are classed at call time by L = len A_i + len B_i;
+// rows without an entry are in no class:
+//   0 packed  L <= kEwisePackedLen  16 lanes per row, two entries a lane at most
+//   1 wave    L <= kEwiseWaveLen    a wave per row, both rows staged in LDS
+//   2 tile    the rest: the row's merge path cut into units of kEwiseTile merged
+//             entries, a workgroup per unit (a cut beside a pair a == b is moved
+//             past the pair's B half: a unit holds one entry more at most)
+constexpr int kEwisePackedLen = 32, kEwiseWaveLen = 512, kEwiseTile = 2048;
+enum { kEwListPacked = 0, kEwListWave, kEwListTile, kEwLists };
+__host__ __device__ inline int ewise_row_list(long long len) {  // -1: no entry, nothing to launch
+    return len <= 0 ? -1 : len <= kEwisePackedLen ? kEwListPacked : len <= kEwiseWaveLen ? kEwListWave : kEwListTile;
+}
+// row pointers, columns in [0, n) and strictly ascending rows of each pattern, on
+// the device before anything indexes with them (tsg_numeric.hip: the plans'
+// checks, for operands that are not a product's); synchronous
+int dev_sorted_patterns_validate(Context &cx, const tsg_dev_csr *const *mats, int nmat, hipStream_t s);
+bool ewise_mode_known(int mode);
+bool binop_known(int op);
+// whether the call reads B's values (a valued call: A.value non-null)
+bool ewise_reads_b_values(int mode, int op);
+// Validates both operands, then runs the pass; synchronous.  A.value null: the
+// structural call.  On TSG_ERR_OVERFLOW (nnz(C) past int32) info.nnzC still
+// holds the exact count.  ev: [4]..[5] bracket the count kernels, [6]..[7] the
+// fill kernels.
+int dev_ewise(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, int mode, int op, double alpha, double beta,
+              tsg_dev_csr &C, tsg_ewise_info &info, hipStream_t s, hipEvent_t *ev);
 
 // read a device int / long long synchronously through pinned memory
 int read_i32(Context &cx, const int *d, int *h, hipStream_t s);

@@ -395,20 +395,23 @@ void dev_numeric_plan_free(NumericPlan &p) {
     p.hmiss = nullptr;
 }
 
-// the validation of A and B, and of a C pattern where there is one (Cp null: the
-// symbolic pass, which has none yet)
-static int validate_patterns(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr *Cp,
-                             bool *b_sorted, hipStream_t s) {
-    if (!shape_ok(A) || !shape_ok(B) || (Cp && !shape_ok(*Cp))) return TSG_ERR_INVALID;
-    if (A.n != B.m || (Cp && (Cp->m != A.m || Cp->n != B.n))) return TSG_ERR_INVALID;
-    const tsg_dev_csr *mats[3] = {&A, &B, Cp};
-    const int nmat = Cp ? 3 : 2;
+// The device checks of up to three patterns, in two host round trips: every
+// row pointer array first (before anything indexes with it), then the columns
+// in range and the rows' order.  order[i]: kOrderAny (rows unchecked),
+// kOrderStrict (strictly ascending or TSG_ERR_INVALID) or kOrderReport (whether
+// they are goes to *reported).  The sortedness checks are queued with a flag
+// each (HostSlots::unsorted), so one wait covers them and the column check.
+enum { kOrderAny = 0, kOrderStrict, kOrderReport };
+static int validate_mats(Context &cx, const tsg_dev_csr *const *mats, const int *order, int nmat, bool *reported,
+                         hipStream_t s) {
+    for (int i = 0; i < nmat; ++i)
+        if (!shape_ok(*mats[i])) return TSG_ERR_INVALID;
     PoolScope ws(cx);  // (the temporaries: returned to the pool on every way out)
     int *bad = nullptr;
     TSG_TRY(ws.get(&bad, 4));
     int hbad[2] = {0, 0};
     TSG_HIP(hipMemsetAsync(bad, 0, 4 * sizeof(int), s));
-    // 1. row pointers, before anything indexes with them
+    // 1. row pointers
     for (int i = 0; i < nmat; ++i) {
         const tsg_dev_csr *M = mats[i];
         k_num_check_rp<<<grid_for((long)M->m + 1, WG, 2048), WG, 0, s>>>(M->rowpointer, M->m, M->nnz, bad);
@@ -417,20 +420,32 @@ static int validate_patterns(Context &cx, const tsg_dev_csr &A, const tsg_dev_cs
     TSG_HIP(hipMemcpyAsync(hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
     TSG_TRY(stream_wait(s));
     if (hbad[0]) return TSG_ERR_INVALID;
-    // 2. columns in range; C's strictly ascending per row; whether B's are
+    // 2. columns in range; the rows' order where it is asked for
     for (int i = 0; i < nmat; ++i) {
         const tsg_dev_csr *M = mats[i];
         if (M->nnz) k_num_check_cols<<<grid_for(M->nnz, WG, 2048), WG, 0, s>>>(M->columnindex, M->nnz, M->n, bad + 1);
+        TSG_HIP(hipGetLastError());
+        if (order[i] != kOrderAny) TSG_TRY(dev_rows_sorted_async(cx, *M, &cx.slots->unsorted[i], s));
     }
-    TSG_HIP(hipGetLastError());
-    bool csorted = true, bsorted = false;
-    if (Cp) TSG_TRY(dev_rows_sorted(cx, *Cp, &csorted, s));
-    TSG_TRY(dev_rows_sorted(cx, B, &bsorted, s));
     TSG_HIP(hipMemcpyAsync(hbad + 1, bad + 1, sizeof(int), hipMemcpyDeviceToHost, s));
     TSG_TRY(stream_wait(s));
-    if (hbad[1] || !csorted) return TSG_ERR_INVALID;
-    *b_sorted = bsorted;
+    if (hbad[1]) return TSG_ERR_INVALID;
+    for (int i = 0; i < nmat; ++i) {
+        const bool sorted = order[i] == kOrderAny || cx.slots->unsorted[i] == 0;
+        if (order[i] == kOrderStrict && !sorted) return TSG_ERR_INVALID;
+        if (order[i] == kOrderReport) *reported = sorted;
+    }
     return TSG_OK;
+}
+
+// the validation of A and B, and of a C pattern where there is one (Cp null: the
+// symbolic pass, which has none yet): C's rows strictly ascending, whether B's are
+static int validate_patterns(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr *Cp,
+                             bool *b_sorted, hipStream_t s) {
+    if (A.n != B.m || (Cp && (Cp->m != A.m || Cp->n != B.n))) return TSG_ERR_INVALID;
+    const tsg_dev_csr *mats[3] = {&A, &B, Cp};
+    const int order[3] = {kOrderAny, kOrderReport, kOrderStrict};
+    return validate_mats(cx, mats, order, Cp ? 3 : 2, b_sorted, s);
 }
 
 int dev_numeric_validate(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, const tsg_dev_csr &Cp,
@@ -440,6 +455,14 @@ int dev_numeric_validate(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B
 
 int dev_operands_validate(Context &cx, const tsg_dev_csr &A, const tsg_dev_csr &B, bool *b_sorted, hipStream_t s) {
     return validate_patterns(cx, A, B, nullptr, b_sorted, s);
+}
+
+// the same checks for patterns that are not a product's (the element-wise pass's
+// operands, three at most): every one's rows strictly ascending
+int dev_sorted_patterns_validate(Context &cx, const tsg_dev_csr *const *mats, int nmat, hipStream_t s) {
+    if (nmat > 3) return TSG_ERR_INVALID;
+    const int order[3] = {kOrderStrict, kOrderStrict, kOrderStrict};
+    return validate_mats(cx, mats, order, nmat, nullptr, s);
 }
 
 // Synchronous (the one-off cost): validation, then the binning on the host from

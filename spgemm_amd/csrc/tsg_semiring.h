@@ -92,4 +92,59 @@ template <class F> static inline int semiring_dispatch(int semiring, F f) {
     }
 }
 
+// ---- the binary ops of the element-wise pass (tsg_ewise.hip): one trait struct
+// per TSG_BINOP_* value.  apply(x, y) combines x = alpha a and y = beta b, each
+// already rounded (ew_scale), and rounds once more: contraction is off in these
+// bodies, so the product and the sum never fuse into an fma (device code is
+// compiled with contraction on).  kReadsA / kReadsB: whether apply reads x / y
+// at all -- the kernels then skip the load and the scaling of the other.
+struct EwPlus {
+    static constexpr bool kReadsA = true, kReadsB = true;
+    static __device__ __forceinline__ double apply(double x, double y) {
+#pragma clang fp contract(off)
+        return x + y;
+    }
+};
+struct EwTimes {
+    static constexpr bool kReadsA = true, kReadsB = true;
+    static __device__ __forceinline__ double apply(double x, double y) {
+#pragma clang fp contract(off)
+        return x * y;
+    }
+};
+struct EwMin {
+    static constexpr bool kReadsA = true, kReadsB = true;
+    static __device__ __forceinline__ double apply(double x, double y) { return fmin(x, y); }
+};
+struct EwMax {
+    static constexpr bool kReadsA = true, kReadsB = true;
+    static __device__ __forceinline__ double apply(double x, double y) { return fmax(x, y); }
+};
+struct EwFirst {
+    static constexpr bool kReadsA = true, kReadsB = false;
+    static __device__ __forceinline__ double apply(double x, double) { return x; }
+};
+struct EwSecond {
+    static constexpr bool kReadsA = false, kReadsB = true;
+    static __device__ __forceinline__ double apply(double, double y) { return y; }
+};
+// scalar * v, rounded once (never the first half of an fma)
+__device__ __forceinline__ double ew_scale(double scalar, double v) {
+#pragma clang fp contract(off)
+    return scalar * v;
+}
+
+// the one switch from a TSG_BINOP_* value to its traits
+template <class F> static inline int binop_dispatch(int op, F f) {
+    switch (op) {
+    case TSG_BINOP_PLUS: return f(EwPlus{});
+    case TSG_BINOP_TIMES: return f(EwTimes{});
+    case TSG_BINOP_MIN: return f(EwMin{});
+    case TSG_BINOP_MAX: return f(EwMax{});
+    case TSG_BINOP_FIRST: return f(EwFirst{});
+    case TSG_BINOP_SECOND: return f(EwSecond{});
+    default: return TSG_ERR_INVALID;
+    }
+}
+
 }  // namespace tsg

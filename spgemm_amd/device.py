@@ -9,7 +9,7 @@ import numpy as np
 
 import weakref
 
-from ._lib import DevCSR, MaskedInfo, NumericInfo, PoolStats, Stats, SymbolicInfo, TsgError, check, lib
+from ._lib import DevCSR, EwiseInfo, MaskedInfo, NumericInfo, PoolStats, Stats, SymbolicInfo, TsgError, check, lib
 from .tilespgemm import SEMIRINGS
 
 _PLUS_PAIR = SEMIRINGS["plus_pair"]
@@ -332,6 +332,55 @@ class Context:
         finally:
             plan.close()
         return DeviceCSR(Cp.m, Cp.n, Cp.rowptr, Cp.col, out), info, st
+
+    def ewise(self, A, B, mode="union", op="plus", alpha=1.0, beta=1.0, stream=None):
+        """The element-wise combination of the DeviceCSRs A and B (one shape,
+        columns strictly ascending per row): C's pattern is A u B ("union"),
+        A n B ("intersect") or A \\ B ("difference"); an entry stored in both
+        holds op(alpha * a, beta * b) (op: a name of tilespgemm.BINOPS), one
+        stored in A alone alpha * a, in B alone beta * b, each rounded once.
+        A.val None: the structural call -- C has no values and none is read
+        (Visited u N of a BFS).  Returns (DevCSR struct with context-owned
+        pointers, info dict, stats dict), valid until the next reset().  mode /
+        op: names, or TSG_EWISE_* / TSG_BINOP_* values passed through (the
+        library refuses unknown ones).  Raises TsgError: TSG_ERR_INVALID for
+        malformed or unsorted operands; TSG_ERR_OVERFLOW when nnz(C) exceeds
+        int32 -- the error's .info then still holds the exact nnzC."""
+        from .tilespgemm import BINOPS, EWISE_MODES
+        a, b, c, info, st = A.struct(), B.struct(), DevCSR(), EwiseInfo(), Stats()
+        s = C.c_void_p(stream) if stream else None
+        md, bo = EWISE_MODES.get(mode, mode), BINOPS.get(op, op)
+        md, bo = (md if isinstance(md, int) else -1), (bo if isinstance(bo, int) else -1)
+        rc = lib().tsg_dev_ewise(self.ptr, C.byref(a), C.byref(b), md, bo, float(alpha), float(beta), s, C.byref(c),
+                                 C.byref(info), C.byref(st))
+        if rc != 0:
+            err = TsgError("tsg_dev_ewise", rc)
+            err.info = info.as_dict()
+            raise err
+        return c, info.as_dict(), st.as_dict()
+
+    def spgemm_accum(self, C0, A, B, semiring="plus_times", accum=None, mask=None, complement=False, stream=None):
+        """C0 (+)= A*B: the product over a semiring (spgemm_semiring; with mask,
+        spgemm_masked_sparse -- C<mask> or, complement=True, C<!mask>, reached
+        entries only) combined with the DeviceCSR C0 by an ewise union with the
+        op accum -- by default the semiring's own sum: "plus", "min" or "max".
+        An entry of C0 the product does not reach is kept as it is, one the
+        product alone holds is taken over.  D = spgemm_accum(D, D, A,
+        semiring="min_plus") is a Bellman-Ford step.  Returns a DeviceCSR in
+        torch tensors."""
+        from .tilespgemm import SEMIRINGS
+        sr = _semiring(semiring)
+        if accum is None:
+            name = {v: k for k, v in SEMIRINGS.items()}.get(sr, "")
+            accum = "min" if name.startswith("min") else "max" if name.startswith("max") else "plus"
+        if mask is None:
+            P, _, _ = self.spgemm_semiring(A, B, sr, stream)
+        else:
+            P, _, _ = self.spgemm_masked_sparse(A, B, mask, complement, sr, stream=stream)
+        if C0.nnz == 0:  # (no values to point at: the library would read the call as structural)
+            return P
+        c, _, _ = self.ewise(C0, P, "union", accum, stream=stream)
+        return self.to_torch(c, device=C0.rowptr.device, stream=stream)
 
     def rows_sorted(self, M, stream=None):
         """whether every row of the device CSR M is strictly column-sorted"""

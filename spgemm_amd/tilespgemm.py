@@ -18,6 +18,7 @@ kernels of libtsg.so through the C ABI (include/tsg.h):
   spgemm_semiring(A, B, semiring)    -> (Matrix, stats)  the full product over a semiring
   spgemm_symbolic_masked(A, B, M, complement, mode) -> (Matrix, stats)  the pattern of A*B inside / outside M
   spgemm_masked_sparse(A, B, M, complement, semiring) -> (Matrix, stats)  C<M> / C<!M>, reached entries only
+  ewise(A, B, mode, op, alpha, beta) -> (Matrix, stats)  element-wise union / intersection / difference
 
 Errors raise TsgError (the reference exits or silently misbehaves instead).
 """
@@ -46,6 +47,12 @@ SYMBOLIC_MODES = {"pattern": SYMBOLIC_PATTERN, "count": SYMBOLIC_COUNT}
 # semirings of the numeric and masked plans (include/tsg.h TSG_SEMIRING_*)
 SEMIRINGS = {"plus_times": 0, "min_plus": 1, "max_plus": 2, "max_times": 3, "max_min": 4, "min_max": 5,
              "plus_pair": 6}
+
+
+PATH_EWISE = 7  # ewise / Context.ewise
+# element-wise modes and binary ops (include/tsg.h TSG_EWISE_* / TSG_BINOP_*)
+EWISE_MODES = {"union": 0, "intersect": 1, "difference": 2}
+BINOPS = {"plus": 0, "times": 1, "min": 2, "max": 3, "first": 4, "second": 5}
 
 
 def semiring_identity(name):
@@ -82,18 +89,22 @@ class Matrix:
 
     @classmethod
     def from_csr(cls, m, n, rowptr, col, val, is_symmetric=0):
+        """A Matrix on the given CSR arrays (kept alive here).  val=None gives a pattern: the
+        value field stays NULL, which the calls that read no values accept (a
+        structural ewise)."""
         o = cls()
         rp = np.ascontiguousarray(rowptr, dtype=np.int32)
         ci = np.ascontiguousarray(col, dtype=np.int32)
-        vv = np.ascontiguousarray(val, dtype=np.float64)
-        if rp.shape[0] != m + 1 or ci.shape[0] != vv.shape[0] or int(rp[-1]) != ci.shape[0]:
+        vv = np.ascontiguousarray(val, dtype=np.float64) if val is not None else None  # (None: a pattern, value NULL)
+        if rp.shape[0] != m + 1 or (vv is not None and ci.shape[0] != vv.shape[0]) or int(rp[-1]) != ci.shape[0]:
             raise ValueError("inconsistent CSR arrays")
         o._keep = [rp, ci, vv]
         o._borrowed = set(_CSR_FIELDS)
         o.s.m, o.s.n, o.s.nnz, o.s.isSymmetric = m, n, ci.shape[0], is_symmetric
         o.s.rowpointer = rp.ctypes.data_as(C.POINTER(C.c_int))
         o.s.columnindex = ci.ctypes.data_as(C.POINTER(C.c_int))
-        o.s.value = vv.ctypes.data_as(C.POINTER(C.c_double))
+        if vv is not None:
+            o.s.value = vv.ctypes.data_as(C.POINTER(C.c_double))
         return o
 
     @classmethod
@@ -258,6 +269,24 @@ def spgemm_masked_sparse(A, B, Mask, complement=False, semiring="plus_times"):
     check("tsg_spgemm_csr_masked_sparse", lib().tsg_spgemm_csr_masked_sparse(
         C.byref(A.s), C.byref(B.s), C.byref(Mask.s), int(complement), SEMIRINGS.get(semiring, semiring),
         C.byref(Cm.s), C.byref(st)))
+    return Cm, st.as_dict()
+
+
+def ewise(A, B, mode="union", op="plus", alpha=1.0, beta=1.0):
+    """Element-wise combination of two Matrices of one shape, both with strictly
+    ascending columns per row: C's pattern is A u B ("union"), A n B
+    ("intersect") or A \\ B ("difference"); an entry stored in both holds
+    op(alpha * a, beta * b) (op: a key of BINOPS), one stored in A alone
+    alpha * a, in B alone beta * b.  A Matrix A without values makes the call
+    structural (C has none either).  mode / op: names, or TSG_EWISE_* /
+    TSG_BINOP_* values.  Returns (C Matrix, stats dict)."""
+    Cm = Matrix()
+    st = Stats()
+    md, bo = EWISE_MODES.get(mode, mode), BINOPS.get(op, op)
+    # (an unknown name reaches the library as -1, as in Context.ewise: it answers TSG_ERR_INVALID)
+    md, bo = (md if isinstance(md, int) else -1), (bo if isinstance(bo, int) else -1)
+    check("tsg_ewise_csr", lib().tsg_ewise_csr(C.byref(A.s), C.byref(B.s), md, bo, float(alpha), float(beta),
+                                               C.byref(Cm.s), C.byref(st)))
     return Cm, st.as_dict()
 
 
